@@ -12,13 +12,19 @@ path: the renderer reads a synthetic stand-in for the regu
 runs inside every timed step and supplies the visibility masks.
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR       (+ the last timed step's outputs as DIR/<name>.npy)
+    python bench.py --full                                                     (+ every secondary figure, see below)
     python bench.py --gpus N                                                   (starts its own N rank processes: launch_ranks below)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N   (one scene per rank, weak scaling; --gpus must equal WORLD_SIZE)
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant HIP kernel, HIP-event
-timed inside the timed region) and `cpu_baseline` (the CPU oracle on a bounded ray sample, rank 0, N=1 only).
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run sets up, warms up, times --steps steps and
+prints the headline (`value`, `ms_per_step` and their spread); the keys of the secondary figures are null there.  With
+--full the same run also reports `roofline` (dominant HIP kernel, HIP-event timed inside the timed region), the kernel
+table, the clocks sampled inside the timed region, `cpu_baseline` (the CPU oracle on a bounded ray sample, rank 0, N=1
+only) and the secondary workloads that follow the timed region.
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -55,11 +61,16 @@ def parse():
     p.add_argument("--shard", default="scenes", choices=["scenes", "rays"],
                    help="N > 1: 'scenes' = one scene per rank (weak scaling, the headline the driver runs); 'rays' = ONE scene whose rays are "
                         "split across the ranks (BASELINE config 4: strong scaling), rendered buffers gathered over RCCL inside the timed region")
-    p.add_argument("--headline-only", action="store_true", help="skip the secondary figures (training steps, validation item, five-level and "
+    p.add_argument("--headline-only", action="store_true", help="with --full: skip the secondary figures (training steps, validation item, five-level and "
                                                                 "split-half variants) that follow the timed region at N = 1")
     p.add_argument("--train-step", action="store_true", help=argparse.SUPPRESS)      # round-1 flag: the training figures are on by default now
     p.add_argument("--sdf-precision", default="f32", choices=["f32", "f16x2"],
                    help="f32: exact float32 MFMA (headline); f16x2: split-half operands on the f16 matrix cores (~1e-6 relative)")
+    p.add_argument("--full", action="store_true", help="besides the headline: kernel timing and table, roofline, clocks, CPU baseline and the "
+                                                       "secondary figures (off: the run does only what the headline needs)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): the image buffers "
+                        "validate() returns, whole, and a fixed seeded sample of every level of K1's cost and mask volumes (rank 0)")
     return p.parse_args()
 
 
@@ -365,13 +376,14 @@ def main():
     import gc
     gc.collect()
     gc.freeze()
-    # HIP events bracket the launches of the dominant kernel inside the timed region (roofline.achieved); the table of all
+    # --full: HIP events bracket the launches of the dominant kernel inside the timed region (roofline.achieved); the table of all
     # kernels comes from one extra, untimed step so that ~600 event records per step do not sit in the measured time
     K1 = "gens_volume_build_levels"         # the north star's own kernel: one launch per step, HIP-event timed inside the timed region like DOMINANT
-    if not args.no_kernel_timing:
+    kernel_timing = args.full and not args.no_kernel_timing
+    if kernel_timing:
         L.profile_begin(only={DOMINANT, K1})
     step_ms = []
-    clocks = ClockSampler(local)
+    clocks = ClockSampler(local) if args.full else contextlib.nullcontext()
     with clocks:
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -380,10 +392,12 @@ def main():
             step_ms.append((time.perf_counter() - t_step) * 1e3)
         sync()
         elapsed = time.perf_counter() - t0
-    kernels, each_launch = L.profile_end(per_launch=True) if not args.no_kernel_timing else ({}, {})
+    kernels, each_launch = L.profile_end(per_launch=True) if kernel_timing else ({}, {})
+    if args.dump_outputs and rank == 0:      # (before any further step replaces the last timed step's outputs)
+        dump_outputs(args.dump_outputs, state["out"], state["cost"], state["masks"])
     headline_chunk = getattr(surf, "last_val_chunk", args.chunk)          # (the secondaries below render other ray counts with the same model)
     timed_steps = {k: args.steps for k in kernels}
-    if not args.no_kernel_timing:
+    if kernel_timing:
         L.profile_begin()
         step()
         sync()
@@ -402,7 +416,7 @@ def main():
     # secondary figure (N > 1, headline = one scene per rank): the SAME run's strong-scaling number -- ONE scene whose rays are split
     # across the ranks (BASELINE config 4), gather inside the timed region.  Every rank takes part (collectives), rank 0 reports.
     ray_sharded = None
-    if dist is not None and (world > 1 or os.environ.get("GENS_BENCH_FORCE_DIST") == "2") and not by_rays and not args.headline_only:
+    if args.full and dist is not None and (world > 1 or os.environ.get("GENS_BENCH_FORCE_DIST") == "2") and not by_rays and not args.headline_only:
         try:
             ray_sharded = ray_sharded_variant(args, dev, dist, surf, volume, n_final, sync)
         except Exception as e:
@@ -492,7 +506,7 @@ def main():
     # f16 hi + lo pair, three f16 MFMAs per product, fp32 accumulate; ~1e-6 relative to the fp32 kernel).
     # Reported beside the headline, never as `value`.
     split = None
-    if world == 1 and args.sdf_precision == "f32" and not args.no_kernel_timing and not args.headline_only:
+    if world == 1 and args.sdf_precision == "f32" and kernel_timing and not args.headline_only:
         surf.sdf_precision = "f16x2"
         step()
         sync()
@@ -523,10 +537,10 @@ def main():
                          "pairs, three f16 MFMAs per product, float32 accumulation, softplus' in float32); not the headline"}
 
     cpu = None
-    if world == 1 and args.cpu_rays > 0:
+    if args.full and world == 1 and args.cpu_rays > 0:
         cpu = cpu_baseline(args, surf, sc, vols, state["masks"], n_final)
 
-    secondary = world == 1 and not args.headline_only
+    secondary = args.full and world == 1 and not args.headline_only
     # secondary figure (N = 1): what one rank of an 8-way ray-sharded image (BASELINE config[3]) has to do, timed alone on this GPU
     projection = None
     if secondary and dist is None and args.sdf_precision == "f32":
@@ -653,7 +667,7 @@ def main():
         "metric": "SDF ray-samples/sec at 480x640, 5-view, 3-scale volumes", "value": value, "unit": "ray-samples/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
         "ms_per_step_stats": percentiles(step_ms), "ms_per_step_by_rank": {"min": round(min(rank_ms), 3), "max": round(max(rank_ms), 3)},
-        "clocks": clocks.summary(),
+        "clocks": clocks.summary() if args.full else None,
         "higher_is_better": True, "scaling": "strong" if by_rays else "weak", "vs_baseline": None,
         "dtype": "f32" if args.sdf_precision == "f32" else "f32 (SDF-MLP operands as split f16 hi+lo pairs, f32 accumulate)", "data": "synthetic",
         "config": {"workload": "BASELINE config[1]: 5-view 480x640, volume_dims=%s, inference of %d rays x %d samples per scene "
@@ -676,6 +690,33 @@ def main():
     }
     os.write(real_stdout, (json.dumps(line) + "\n").encode())
     finish()
+
+
+DUMP_SAMPLE = 1 << 20            # elements kept of every level of K1's cost and mask volumes (the 256^3 level alone is 537 MB of cost volume)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, out, cost_volumes, masks):
+    """--dump-outputs: what the last timed step computed, as float32 DIR/<name>.npy.  The image buffers validate() hands its caller
+    (color_fine, img_fine, normal_img, sdf_depth, render_depth) are written whole; of every level i of K1's outputs the same DUMP_SAMPLE flat
+    indices on every run (a generator seeded with i) -> cost_volume_l<i>, mask_volume_l<i> (mask as 0 / 1)."""
+    import numpy as np
+    arrays = {}
+    for name, v in out.items():
+        arrays[name] = np.ascontiguousarray((v.numpy() if torch.is_tensor(v) else np.asarray(v)).astype(np.float32))
+    for i, (c, m) in enumerate(zip(cost_volumes, masks)):
+        for name, t in (("cost_volume_l%d" % i, c), ("mask_volume_l%d" % i, m)):
+            flat = t.detach().reshape(-1)
+            if flat.numel() > DUMP_SAMPLE:
+                g = torch.Generator().manual_seed(i)
+                flat = flat[torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).to(flat.device)]
+            arrays[name] = flat.float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %.1f MB (limit %d MB)" % (total / 2 ** 20, DUMP_LIMIT_BYTES >> 20))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def kernel_rows(table, top):

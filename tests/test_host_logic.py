@@ -88,11 +88,43 @@ def test_bench_command_line_contract():
         a = bench.parse()
         assert (a.gpus, a.steps, a.warmup, a.rays, a.dims, a.views) == (1, 10, 3, 480 * 640, [256, 128, 64], 5)
         assert a.sdf_precision == "f32" and not a.train_step and not a.no_kernel_timing
+        assert not a.full and a.dump_outputs is None                     # a plain run measures the headline only and writes nothing
         sys.argv = ["bench.py", "--gpus", "8", "--steps", "5", "--warmup", "2"]
         a = bench.parse()
         assert (a.gpus, a.steps, a.warmup) == (8, 5, 2)
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "out_dir"]
+        a = bench.parse()
+        assert a.full and a.dump_outputs == "out_dir"
     finally:
         sys.argv = saved
+
+
+def test_bench_dump_outputs_writes_float32_arrays_and_the_same_sample_every_time(tmp_path, monkeypatch):
+    """--dump-outputs: the image buffers whole, a fixed seeded sample of every K1 level, float32, under the size limit."""
+    import importlib
+    import sys
+    import numpy as np
+    root = __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(bench, "torch", torch)                        # (main() sets it in a rank process)
+    g = torch.Generator().manual_seed(0)
+    out = {"color_fine": torch.rand(40, 3, generator=g), "render_depth": np.random.default_rng(0).random((1, 40)).astype(np.float32)}
+    cost = [torch.rand(1, 8, 64, 64, 64, generator=g), torch.rand(1, 8, 8, 8, 8, generator=g)]
+    masks = [torch.rand(1, 1, 64, 64, 64, generator=g) > 0.5, torch.rand(1, 1, 8, 8, 8, generator=g) > 0.5]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), out, cost, masks)
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["color_fine.npy", "cost_volume_l0.npy", "cost_volume_l1.npy", "mask_volume_l0.npy", "mask_volume_l1.npy", "render_depth.npy"]
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+    assert np.array_equal(np.load(tmp_path / "a" / "color_fine.npy"), out["color_fine"].numpy())
+    assert np.load(tmp_path / "a" / "cost_volume_l0.npy").shape == (bench.DUMP_SAMPLE,)          # 2 M elements: sampled
+    assert np.array_equal(np.load(tmp_path / "a" / "cost_volume_l1.npy"), cost[1].reshape(-1).numpy())   # 4 096: whole
+    m0 = np.load(tmp_path / "a" / "mask_volume_l0.npy")
+    assert np.array_equal(m0, masks[0].reshape(-1).float().numpy()) and set(np.unique(m0)) <= {0.0, 1.0}      # 262 144: whole, as 0 / 1
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
