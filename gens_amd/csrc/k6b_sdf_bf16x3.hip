@@ -1,0 +1,581 @@
+// K6b: the SDF network on the bf16 matrix cores with THREE-TERM split operands -- value only (the sampling passes of
+// the reference's models/modules/implicit_surface.py:125, 329-352) and value AND gradient d sdf / dx (render_core's 128 samples per ray:
+// implicit_surface.py:179-191 -> sdf_network.py:98-154), float32-accurate, the default "f32" arithmetic at three and five volume levels.
+//
+//   * every float32 operand is x = x0 + x1 + x2, three round-to-nearest bf16 terms (v_cvt_pk_bf16_f32; x - x0 and x - x0 - x1 are exact
+//     in float32): 24+ bits of significand and float32's exponent range -- nothing can overflow, no flag, no re-run.  A product is the six
+//     terms x2 y0, x1 y1, x0 y2, x1 y0, x0 y1, x0 y0 on v_mfma_f32_32x32x16_bf16 (smallest first, float32 accumulation; each bf16 x bf16
+//     product is exact in float32); the three dropped terms are below ~2^-26 relative.  6 x 32 cycles per 32 x 32 x 16 block against
+//     8 x 64 of v_mfma_f32_32x32x2_f32.
+//   * the dataflow of k6gh_sdf_grad_f16.hip: one wavefront owns 32 points and all 128 hidden units; the weights are the A operand, the
+//     activations the B operand; the activated accumulators of a layer, split, ARE the B operands of the next one (registers 8 s .. 8 s + 7
+//     of a tile are K step s; the host packs the reduction index in that order).  The reverse pass is the same chain on the transposed
+//     matrices, G_{l-1} = (W_l^T G_l) * softplus'(a_{l-1}), split the same way.  The weight stream (1 KB pieces: one term of the A operand
+//     of one output tile and one 16-deep K block) goes global -> LDS once per workgroup of four waves, by LDS-direct buffer loads into a
+//     ring of four 8 KB chunks filled three chunks ahead.
+//   * the value kernel is the forward half of the same code (GRAD = false) reading the forward prefix of the same stream: the two kernels
+//     issue the same MFMAs in the same order on the same operands, so they return the SAME float32 sdf for the same point.
+//   * softplus and softplus' (float32), the trilinear look-up and its Jacobians, the stash of layer 2's softplus' and the chain rule to x
+//     are k6gh's; the gradients need no scaling (bf16 has float32's range).
+#include "common.h"
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x2v __attribute__((ext_vector_type(2)));
+typedef float f32x4v __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+#define GB_WAVES 4
+#define GB_PIECE 1024                       // bytes of one piece: 64 lanes x 8 bf16
+#define GB_TERMS 3                          // pieces per (K block, output tile): x0, x1, x2
+#define GB_CH 8                             // pieces per chunk of the ring
+#define GB_RING 4
+#define GB_GT 2                             // output tiles per group of A operands
+#define GB_LPW (GB_CH / GB_WAVES)           // LDS-direct loads per wave and chunk
+#define GB_W_BYTES (GB_RING * GB_CH * GB_PIECE)
+#define GB_D_BYTES (2 * 16 * 64 * 16)       // softplus' of layers 0 and 1 of one wave
+#define GB_LDS_BYTES (GB_W_BYTES + GB_WAVES * GB_D_BYTES)
+#define GB_JL_OFF 16384                     // stash slot: [0, 16 KB) softplus' of layer 2, then 32 rows x 256 B of Jacobians, then the lock
+#define GB_LOCK_OFF (GB_JL_OFF + 32 * 256)
+#define GB_SLOT_BYTES (GB_LOCK_OFF + 256)
+#define GB_SLOTS 2048                       // (XCC 3 bits, SE 2, CU 4, wave 2)
+#define GB_C 144.26950408889634f            // 100 / ln 2: hidden units travel as c * softplus (k6_sdfmlp.hip::softplus_t)
+
+struct Split3Block {      // the B operand of one 16-deep K block: this lane's 8 values as three bf16 terms
+    u32x4 p[GB_TERMS];
+};
+
+struct Split3Word {
+    uint32_t w[GB_TERMS];
+};
+__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {      // v_cvt_pk_bf16_f32: a -> bits [15:0], b -> [31:16], nearest even
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2v){a, b}, bf16x2));
+}
+// (a, b) -> their three packed terms; the residuals a - x0, a - x0 - x1 are exact in float32
+__device__ __forceinline__ Split3Word split3_pair(float a, float b) {
+    Split3Word s;
+#pragma unroll
+    for (int k = 0; k < GB_TERMS; ++k) {
+        const uint32_t w = pk_bf16(a, b);
+        s.w[k] = w;
+        if (k + 1 < GB_TERMS) {
+            a -= __builtin_bit_cast(float, w << 16);
+            b -= __builtin_bit_cast(float, w & 0xffff0000u);
+        }
+    }
+    return s;
+}
+#define GB_PUT(BLK_, W_, A_, B_)                                            \
+    {                                                                       \
+        const Split3Word sw__ = split3_pair((A_), (B_));                    \
+        _Pragma("unroll") for (int k__ = 0; k__ < GB_TERMS; ++k__) (BLK_).p[k__][(W_)] = sw__.w[k__]; \
+    }
+
+// value of one packed (X, Y, Z, 4) volume at x and its derivative with respect to x (zero padding, align_corners=True)
+__device__ __forceinline__ float4 sample_volume4b(const float4* __restrict__ v, int Xd, int Yd, int Zd, const float x[3], bool live, float4& jx,
+                                                  float4& jy, float4& jz) {
+    float w0[3], w1[3];
+    int i0[3];
+    bool in0[3], in1[3];
+    const int sz[3] = {Xd, Yd, Zd};
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float pos = (x[a] + 1.0f) / 2.0f * (float)(sz[a] - 1);
+        const float f = fminf(fmaxf(floorf(pos), -2.0f), (float)sz[a] + 1.0f);
+        i0[a] = (int)f;
+        w0[a] = (f + 1.0f) - pos;
+        w1[a] = pos - f;
+        in0[a] = i0[a] >= 0 && i0[a] < sz[a];
+        in1[a] = i0[a] + 1 >= 0 && i0[a] + 1 < sz[a];
+    }
+    float4 acc = f4_zero();
+    jx = f4_zero(); jy = f4_zero(); jz = f4_zero();
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const int a = c >> 2, b = (c >> 1) & 1, d = c & 1;
+        const bool ok = live && (a ? in1[0] : in0[0]) && (b ? in1[1] : in0[1]) && (d ? in1[2] : in0[2]);
+        const int cx = min(max(i0[0] + a, 0), Xd - 1), cy = min(max(i0[1] + b, 0), Yd - 1), cz = min(max(i0[2] + d, 0), Zd - 1);
+        float4 t = v[((int64_t)cx * Yd + cy) * Zd + cz];
+        if (!ok) t = f4_zero();
+        const float wx = a ? w1[0] : w0[0], wy = b ? w1[1] : w0[1], wz = d ? w1[2] : w0[2];
+        acc = f4_madd(acc, t, wx * wy * wz);
+        jx = f4_madd(jx, t, (a ? 1.0f : -1.0f) * wy * wz);
+        jy = f4_madd(jy, t, wx * (b ? 1.0f : -1.0f) * wz);
+        jz = f4_madd(jz, t, wx * wy * (d ? 1.0f : -1.0f));
+    }
+    const float sx = (float)(Xd - 1) / 2.0f, sy = (float)(Yd - 1) / 2.0f, sz_ = (float)(Zd - 1) / 2.0f;
+    jx.x *= sx; jx.y *= sx; jx.z *= sx; jx.w *= sx;
+    jy.x *= sy; jy.y *= sy; jy.z *= sy; jy.w *= sy;
+    jz.x *= sz_; jz.y *= sz_; jz.z *= sz_; jz.w *= sz_;
+    return acc;
+}
+
+// The piece stream, in the order the kernels consume it (gens_amd.ops._pack_grad_pieces(..., terms=3)): k6gh's order with three pieces
+// (x0, x1, x2) per (K block, output tile) instead of (hi, lo).  The value kernel reads the forward part only.
+template <int NLEV>
+struct GradShapeB {
+    static constexpr int CF = 4 * NLEV;
+    static constexpr int NCH = CF / 2;                     // channels per lane half
+    static constexpr int NC = (5 * NCH + 1 + 7) / 8;       // conditioning K blocks: 5 encodings per channel + the constant-one slot
+    static constexpr int TC = (5 * NCH + 15) / 16;         // accumulator tiles of the conditioning gradient (16 slots of a half per tile)
+    static constexpr int BLK = 4 * GB_TERMS;               // pieces of one forward K block
+    static constexpr int fwd(int l) { return l == 0 ? 0 : BLK * (2 + (l - 1) * (NC + 8) + (l > 3 ? 2 : 0)); }      // first piece of forward layer l
+    static constexpr int FWD_PIECES = fwd(5) + BLK * (NC + 8);
+    static constexpr int rev_tiles(int l) { return 4 + TC + (l == 3 ? 1 : 0); }
+    static constexpr int rev_blocks(int l) { return l == 2 ? 7 : 8; }
+    static constexpr int rev(int l) {      // first piece of reverse layer l = 5 .. 1; rev(0): the G_0 blocks
+        int p = FWD_PIECES;
+        for (int k = 5; k > l; --k) p += GB_TERMS * rev_tiles(k) * rev_blocks(k);
+        return p;
+    }
+    static constexpr int PIECES = rev(0) + 8 * GB_TERMS;
+    static constexpr int NCHUNK = (PIECES + GB_CH - 1) / GB_CH;
+    static constexpr int NCHUNK_FWD = (FWD_PIECES + GB_CH - 1) / GB_CH;
+};
+
+template <int NLEV, bool GRAD>
+__global__ __launch_bounds__(64 * GB_WAVES, 1) void sdf_bf16x3_k(LevelSet vols, const char* __restrict__ pieces, const float* w_out, float b_last,
+                                                                 float scale, float inv_scale, const float* __restrict__ pts,
+                                                                 const int64_t* __restrict__ index, int64_t n_max, const int32_t* __restrict__ n_dev,
+                                                                 float* __restrict__ sdf_out, float* __restrict__ grad_out,
+                                                                 char* __restrict__ stash_all) {
+    typedef GradShapeB<NLEV> S;
+    constexpr int NCH = S::NCH, NC = S::NC, TC = S::TC, MID = NLEV / 2;
+    constexpr int NCHUNK = GRAD ? S::NCHUNK : S::NCHUNK_FWD;
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n_pt = lane & 31, half = lane >> 5;
+    const int64_t n = n_dev ? min(n_max, (int64_t)n_dev[0]) : n_max;
+    const int64_t m0 = (int64_t)blockIdx.x * (32 * GB_WAVES);
+    if (m0 >= n) return;
+    float4* const DS = (float4*)(lds + GB_W_BYTES + wave * GB_D_BYTES);       // [layer][accumulator register / 4][lane]  (GRAD only)
+
+    // chunk c of the stream -> ring slot c % GB_RING: wave w brings pieces w, w + 4, .. (LDS-direct buffer loads: the piece's offset in
+    // the stream is a scalar, 16 lane the one vector offset, lane i lands at the piece's base in LDS + 16 i)
+    const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc((void*)pieces, 0, NCHUNK * GB_CH * GB_PIECE, 0x00020000);
+    const uint32_t lane16 = (uint32_t)lane * 16u;
+    auto stage = [&](int c) {
+        char* dst = lds + (c % GB_RING) * (GB_CH * GB_PIECE);
+#pragma unroll
+        for (int p = 0; p < GB_LPW; ++p) {
+            const int piece = wave + GB_WAVES * p;
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(prs, (__attribute__((address_space(3))) void*)(dst + piece * GB_PIECE), 16, lane16,
+                                                     (uint32_t)(c * (GB_CH * GB_PIECE) + piece * GB_PIECE), 0, 0);
+        }
+    };
+#pragma unroll
+    for (int c = 0; c < GB_RING - 1; ++c) stage(c);
+
+    // this wave's slot of the stash (one workgroup per CU -- the LDS allocation sees to it -- so (CU, wave) is unique; the lock word
+    // makes that a performance assumption instead of a correctness one)
+    uint32_t* lock = nullptr;
+    uint32_t lock_seen = 0u;
+    __amdgpu_buffer_rsrc_t stash;
+    if constexpr (GRAD) {
+        uint32_t hw_id, xcc_id;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_id));          // [11:8] CU, [15:13] SE (scripts/probe/hwid_probe.py)
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc_id));
+        const uint32_t slot = ((((xcc_id & 7u) << 2 | ((hw_id >> 13) & 3u)) << 4 | ((hw_id >> 8) & 15u)) << 2) | (uint32_t)wave;
+        char* const stash_slot = stash_all + (size_t)slot * GB_SLOT_BYTES;
+        lock = (uint32_t*)(stash_slot + GB_LOCK_OFF);
+        lock_seen = lane == 0 ? atomicCAS(lock, 0u, 1u) : 0u;      // (asked for here, looked at before the first store into the slot)
+        stash = __builtin_amdgcn_make_buffer_rsrc((void*)stash_slot, 0, GB_LOCK_OFF, 0x00020000);
+    }
+    const uint32_t stash_lane = (uint32_t)lane * 16u, jl_lane = GB_JL_OFF + (uint32_t)lane * 4u;
+
+    // ------------------------------------------------------------------ prologue: this lane's B-operand slots
+    const int64_t row = m0 + 32 * wave + n_pt;
+    const bool live = row < n;
+    const int64_t src = live ? (index ? index[row] : row) : 0;
+    float x[3] = {0.f, 0.f, 0.f};
+    if (live) { x[0] = pts[3 * src]; x[1] = pts[3 * src + 1]; x[2] = pts[3 * src + 2]; }
+    float nan_sum = 0.0f;      // not-a-number inputs must come out as not-a-number: see the poison term below
+
+    Split3Block P[2];     // point encoding: half 0 = x, octaves 0 and 1, ONE; half 1 = octaves 2 and 3, zeros
+    {
+        float q[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) q[k] = 0.0f;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float v = x[a] * scale;
+            float s0, c0, s1, c1;
+            hw_sincos(v * (half ? 4.0f : 1.0f), s0, c0);
+            hw_sincos(v * (half ? 8.0f : 2.0f), s1, c1);
+            if (half == 0) {
+                q[a] = v; q[3 + a] = s0; q[6 + a] = c0; q[9 + a] = s1; q[12 + a] = c1;
+            } else {
+                q[a] = s0; q[3 + a] = c0; q[6 + a] = s1; q[9 + a] = c1;
+            }
+            nan_sum += x[a];
+        }
+        if (half == 0) q[15] = 1.0f;
+#pragma unroll
+        for (int k = 0; k < 16; k += 2) GB_PUT(P[k >> 3], (k & 7) >> 1, q[k], q[k + 1])
+    }
+
+    Split3Block C[NC];    // volume features: 5 encodings of this half's NCH channels, then ONE (half 0), then zeros
+    const float* wo = w_out + half * (64 + 16 * TC);
+    float s_cond = 0.0f;
+    float f[NCH];        // the raw features: the chain rule at the end re-derives the encodings from them
+    {
+        float jl[3 * NCH];
+#pragma unroll
+        for (int j = 0; j <= MID; ++j) {     // whole levels of this half (j < MID); level MID is shared, two channels each
+            const int l = j < MID ? (half ? MID + 1 + j : j) : MID;
+            float4 jx, jy, jz;
+            const float4 t = sample_volume4b((const float4*)vols.data[l], vols.dx[l], vols.dy[l], vols.dz[l], x, live, jx, jy, jz);
+            float tv[4] = {t.x, t.y, t.z, t.w}, ax[4] = {jx.x, jx.y, jx.z, jx.w}, ay[4] = {jy.x, jy.y, jy.z, jy.w}, az[4] = {jz.x, jz.y, jz.z, jz.w};
+            if (j == MID && half) {
+                tv[0] = tv[2]; tv[1] = tv[3]; ax[0] = ax[2]; ax[1] = ax[3]; ay[0] = ay[2]; ay[1] = ay[3]; az[0] = az[2]; az[1] = az[3];
+            }
+#pragma unroll
+            for (int c = 0; c < (j < MID ? 4 : 2); ++c) {
+                const int ch = 4 * j + c;
+                f[ch] = tv[c];
+                jl[3 * ch] = ax[c]; jl[3 * ch + 1] = ay[c]; jl[3 * ch + 2] = az[c];
+            }
+        }
+        if constexpr (GRAD) {
+            if (lane == 0) gens_lock_slot(lock, lock_seen);
+#pragma unroll
+            for (int k = 0; k < 3 * NCH; ++k) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, jl[k]), stash, jl_lane + (uint32_t)k * 256u, 0, 0);
+        }
+        float e[8 * NC];
+#pragma unroll
+        for (int k = 5 * NCH; k < 8 * NC; ++k) e[k] = (k == 5 * NCH && half == 0) ? 1.0f : 0.0f;
+#pragma unroll
+        for (int j = 0; j < NCH; ++j) {
+            e[5 * j] = f[j];
+            hw_sincos(f[j], e[5 * j + 1], e[5 * j + 2]);
+            hw_sincos(2.0f * f[j], e[5 * j + 3], e[5 * j + 4]);
+            nan_sum += f[j];
+#pragma unroll
+            for (int q = 0; q < 5; ++q) s_cond = __builtin_fmaf(e[5 * j + q], wo[64 + 5 * j + q], s_cond);       // layer 6 reads the conditioning features too
+        }
+#pragma unroll
+        for (int k = 0; k < 8 * NC; k += 2) GB_PUT(C[k >> 3], (k & 7) >> 1, e[k], e[k + 1])
+    }
+
+    f32x16 acc[4];                 // the product being accumulated
+    Split3Block H[8];              // the operand of the running product: activations, then G_l (block 2 t + (r >> 3), slot r & 7 <- tile t, register r)
+    f32x16 D3[4], D4[4];           // softplus' of layers 3, 4 (GRAD)
+    f32x16 gc[TC], gp;             // d sdf / d (this lane's conditioning slots), d sdf / d (its point-encoding slots)
+    u32x4 abuf[2][GB_TERMS * GB_GT];      // A operands: this group's and the next one's
+    int par = 0;                   // (compile-time after unrolling, like every index below)
+    int dirty = GRAD ? 1 : 0;      // stores are outstanding: the next chunk boundary waits for everything
+
+    // chunk boundary: this wave's share of chunk C_ has landed (its later chunks may still be in flight), every wave says so, and the
+    // ring slot everyone has just finished reading is refilled three chunks ahead
+#define GB_BOUNDARY(C_)                                                                                  \
+    {                                                                                                    \
+        const int c__ = (C_);                                                                            \
+        const int later__ = (c__ + GB_RING - 2 < NCHUNK - 1 ? c__ + GB_RING - 2 : NCHUNK - 1) - c__;     \
+        if (dirty || later__ <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                      \
+        else if (later__ == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GB_LPW) : "memory");             \
+        else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * GB_LPW) : "memory");                           \
+        dirty = 0;                                                                                       \
+        __builtin_amdgcn_s_barrier();                                                                    \
+        asm volatile("" ::: "memory");                                                                   \
+        if (c__ + GB_RING - 1 < NCHUNK) stage(c__ + GB_RING - 1);                                        \
+    }
+    // pieces P0_ .. P0_ + CNT_ -> A register set SET_
+#define GB_LOAD(SET_, P0_, CNT_)                                                                         \
+    _Pragma("unroll") for (int j_ = 0; j_ < GB_TERMS * GB_GT; ++j_) if (j_ < (CNT_)) {                    \
+        const int p_ = (P0_) + j_;                                                                       \
+        if (p_ % GB_CH == 0) GB_BOUNDARY(p_ / GB_CH)                                                     \
+        abuf[SET_][j_] = *((const u32x4*)(lds + ((p_ / GB_CH) % GB_RING) * (GB_CH * GB_PIECE) + (p_ % GB_CH) * GB_PIECE) + lane); \
+    }
+#define GB_MFMA(ACC_, A_, B_) ACC_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, (A_)), __builtin_bit_cast(bf16x8, (B_)), ACC_, 0, 0, 0)
+    // accumulator of output tile T_ of a reverse K block: hidden tiles, conditioning tiles, the point-encoding tile
+#define GB_RACC(T_) (*((T_) < 4 ? &acc[(T_) < 4 ? (T_) : 0] : (T_) < 4 + TC ? &gc[(T_) < 4 + TC && (T_) >= 4 ? (T_) - 4 : 0] : &gp))
+    // the six products of one operand pair, smallest first: weight term WA_ x activation term WB_
+#define GB_TERM(WA_, WB_, REV_, B_)                                                                      \
+    _Pragma("unroll") for (int t_ = 0; t_ < GB_GT; ++t_) if (t_ < nt_) {                                 \
+        if (REV_) GB_MFMA(GB_RACC(t0_ + t_), abuf[par][GB_TERMS * t_ + (WA_)], (B_)[i_].p[(WB_)]);       \
+        else GB_MFMA(acc[(t0_ + t_) & 3], abuf[par][GB_TERMS * t_ + (WA_)], (B_)[i_].p[(WB_)]);          \
+    }
+    // CNT_ K blocks of NT_ output tiles from piece P0_ on, B operands B_[0 .. CNT_); REV_: the accumulators of a reverse block.  The A
+    // operands arrive in groups of GB_GT tiles (three terms each), one group ahead of the MFMAs that read them.  Within a group the
+    // accumulators alternate.
+#define GB_SEGMENT(P0_, CNT_, NT_, B_, REV_)                                                             \
+    {                                                                                                    \
+        constexpr int ng__ = ((NT_) + GB_GT - 1) / GB_GT;      /* (CNT_ and NT_ are constant expressions at every call) */ \
+        GB_LOAD(par, (P0_), GB_TERMS * ((NT_) < GB_GT ? (NT_) : GB_GT))                                  \
+        _Pragma("unroll") for (int q_ = 0; q_ < (CNT_) * ng__; ++q_) {                                   \
+            const int i_ = q_ / ng__, t0_ = (q_ % ng__) * GB_GT, nt_ = (NT_) - t0_ < GB_GT ? (NT_) - t0_ : GB_GT; \
+            if (q_ + 1 < (CNT_) * ng__) {                                                                \
+                const int i2_ = (q_ + 1) / ng__, t2_ = ((q_ + 1) % ng__) * GB_GT, n2_ = (NT_) - t2_ < GB_GT ? (NT_) - t2_ : GB_GT; \
+                GB_LOAD(par ^ 1, (P0_) + GB_TERMS * ((NT_) * i2_ + t2_), GB_TERMS * n2_)                  \
+            }                                                                                            \
+            __builtin_amdgcn_sched_barrier(0);                                                           \
+            GB_TERM(2, 0, REV_, B_) GB_TERM(1, 1, REV_, B_) GB_TERM(0, 2, REV_, B_)                      \
+            GB_TERM(1, 0, REV_, B_) GB_TERM(0, 1, REV_, B_) GB_TERM(0, 0, REV_, B_)                      \
+            __builtin_amdgcn_sched_barrier(0);                                                           \
+            par ^= 1;                                                                                    \
+        }                                                                                                \
+    }
+#define GB_ZERO()                                             \
+    _Pragma("unroll") for (int t_ = 0; t_ < 4; ++t_)          \
+        _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) acc[t_][r_] = 0.0f;
+    // h~ = c softplus(a) = log2(1 + 2^t) and softplus' = 2^t / (1 + 2^t) of one accumulator tile (k6g_sdf_grad.hip: no compare masks, 16
+    // independent instructions of one kind back to back)
+#define GB_SOFTPLUS_TILE(T_, HT_, DT_)                                                                     \
+    {                                                                                                      \
+        f32x16 e__, u__, r__;                                                                              \
+        _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) e__[r_] = __builtin_amdgcn_exp2f(__builtin_amdgcn_fmed3f((T_)[r_], 126.0f, -3.0e38f)); \
+        _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) u__[r_] = 1.0f + e__[r_];                        \
+        if (GRAD) { _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) r__[r_] = __builtin_amdgcn_rcpf(u__[r_]); } \
+        _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) u__[r_] = __builtin_amdgcn_logf(u__[r_]);        \
+        if (GRAD) { _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) (DT_)[r_] = e__[r_] * r__[r_]; }     \
+        _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) (HT_)[r_] = __builtin_amdgcn_fmed3f((T_)[r_], u__[r_], 3.0e38f); \
+    }
+    // the 16 values of tile T_ -> K blocks 2 T_, 2 T_ + 1 of H
+#define GB_SPLIT_TILE(T_, V_)                                                                              \
+    _Pragma("unroll") for (int r_ = 0; r_ < 16; r_ += 2) GB_PUT(H[2 * (T_) + (r_ >> 3)], (r_ & 7) >> 1, (V_)[r_], (V_)[r_ + 1])
+
+    // ------------------------------------------------------------------ forward
+    float s_val = s_cond;
+    GB_ZERO();
+    GB_SEGMENT(S::fwd(0), 2, 4, P, false);
+#pragma unroll
+    for (int l = 0; l < 6; ++l) {
+        if (l > 0) {
+            GB_ZERO();
+            GB_SEGMENT(S::fwd(l), NC, 4, C, false);
+            if (l == 3) GB_SEGMENT(S::fwd(3) + S::BLK * NC, 2, 4, P, false);
+            GB_SEGMENT(S::fwd(l) + S::BLK * (NC + (l == 3 ? 2 : 0)), 8, 4, H, false);
+        }
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            f32x16 h, d;
+            if (l == 3) {
+                GB_SOFTPLUS_TILE(acc[t], h, D3[t]);
+            } else if (l == 4) {
+                GB_SOFTPLUS_TILE(acc[t], h, D4[t]);
+            } else {
+                GB_SOFTPLUS_TILE(acc[t], h, d);
+            }
+            if constexpr (GRAD) {
+                if (l < 2) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) DS[(l * 16 + 4 * t + q) * 64 + lane] = make_float4(d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]);
+                }
+                if (l == 2) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)      // (the register's offset in the VECTOR offset: see k6g_sdf_grad.hip)
+                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, (f32x4v){d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]}), stash,
+                                                               stash_lane + (uint32_t)(4 * t + q) * 1024u, 0, 0);
+                    dirty = 1;
+                }
+            }
+            if (l < 5) {
+                GB_SPLIT_TILE(t, h);
+            } else {    // layer 6 is one row: the value is a dot product, and G_5 = w_last * softplus' starts the reverse pass
+                f32x16 g;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const float w = wo[16 * t + r];                      // w_last / c in this lane's accumulator order
+                    s_val = __builtin_fmaf(h[r], w, s_val);
+                    if (GRAD) g[r] = (w * GB_C) * d[r];
+                }
+                if constexpr (GRAD) GB_SPLIT_TILE(t, g);
+            }
+        }
+    }
+    // not-a-number inputs must come out as not-a-number (the reference's layers propagate them; the max / median forms of the activation drop
+    // them): a poison term 0 * (sum of the inputs), NaN iff one of them is NaN or infinite
+    s_val += 0.0f * nan_sum;
+    s_val += __shfl_xor(s_val, 32, 64);
+
+    if constexpr (!GRAD) {
+        if (half == 0 && live) sdf_out[src] = (s_val + b_last) * inv_scale;
+    } else {
+        // ------------------------------------------------------------------ reverse pass
+#pragma unroll
+        for (int c = 0; c < TC; ++c)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) gc[c][r] = (16 * c + r < 5 * NCH) ? wo[64 + 16 * c + r] : 0.0f;      // layer 6 reads the features directly
+#pragma unroll
+        for (int r = 0; r < 16; ++r) gp[r] = 0.0f;
+#pragma unroll
+        for (int l = 5; l >= 1; --l) {
+            GB_ZERO();
+            if (l == 3) {      // softplus' of layer 2 comes back into the registers layer 4's has left (requested before the products that hide the trip)
+#pragma unroll
+                for (int t = 0; t < 4; ++t)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const f32x4v v = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(stash, stash_lane + (uint32_t)(4 * t + q) * 1024u, 0, 0));
+                        D4[t][4 * q] = v[0]; D4[t][4 * q + 1] = v[1]; D4[t][4 * q + 2] = v[2]; D4[t][4 * q + 3] = v[3];
+                    }
+            }
+            if (l == 3) {
+                GB_SEGMENT(S::rev(3), 8, 4 + TC + 1, H, true);
+            } else if (l == 2) {
+                GB_SEGMENT(S::rev(2), 7, 4 + TC, H, true);
+            } else {
+                GB_SEGMENT(S::rev(l), 8, 4 + TC, H, true);
+            }
+            // G_{l-1} = (W_l^T G_l) * softplus'(a_{l-1})
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                f32x16 g;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    float4 d;
+                    if (l == 5) d = make_float4(D4[t][4 * q], D4[t][4 * q + 1], D4[t][4 * q + 2], D4[t][4 * q + 3]);
+                    if (l == 4) d = make_float4(D3[t][4 * q], D3[t][4 * q + 1], D3[t][4 * q + 2], D3[t][4 * q + 3]);
+                    if (l == 3) d = make_float4(D4[t][4 * q], D4[t][4 * q + 1], D4[t][4 * q + 2], D4[t][4 * q + 3]);
+                    if (l == 2) d = DS[(16 + 4 * t + q) * 64 + lane];
+                    if (l == 1) d = DS[(4 * t + q) * 64 + lane];
+                    g[4 * q] = acc[t][4 * q] * d.x;
+                    g[4 * q + 1] = acc[t][4 * q + 1] * d.y;
+                    g[4 * q + 2] = acc[t][4 * q + 2] * d.z;
+                    g[4 * q + 3] = acc[t][4 * q + 3] * d.w;
+                }
+                GB_SPLIT_TILE(t, g);
+            }
+        }
+        {   // layer 0 reads the point encoding only: the six products in five independent chains, added smallest first at the end
+            GB_ZERO();
+            GB_LOAD(par, S::rev(0), GB_TERMS)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                if (i + 1 < 8) { GB_LOAD(par ^ 1, S::rev(0) + GB_TERMS * (i + 1), GB_TERMS) }
+                __builtin_amdgcn_sched_barrier(0);
+                GB_MFMA(acc[0], abuf[par][2], H[i].p[0]);
+                GB_MFMA(acc[1], abuf[par][1], H[i].p[1]);
+                GB_MFMA(acc[2], abuf[par][1], H[i].p[0]);
+                GB_MFMA(acc[0], abuf[par][0], H[i].p[2]);
+                GB_MFMA(acc[3], abuf[par][0], H[i].p[1]);
+                GB_MFMA(gp, abuf[par][0], H[i].p[0]);
+                __builtin_amdgcn_sched_barrier(0);
+                par ^= 1;
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) gp[r] += (acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r]);
+        }
+
+        // ------------------------------------------------------------------ chain rule to x, lane-local (sdf_network.py:131-154)
+        {
+            float g[3];
+#pragma unroll
+            for (int a = 0; a < 3; ++a) asm volatile("" : "+v"(x[a]));      // (opaque: or the compiler keeps the prologue's encodings alive instead)
+#pragma unroll
+            for (int j = 0; j < NCH; ++j) asm volatile("" : "+v"(f[j]));
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                const float v = x[a] * scale;
+                float s0, c0, s1, c1;
+                hw_sincos(v * (half ? 4.0f : 1.0f), s0, c0);
+                hw_sincos(v * (half ? 8.0f : 2.0f), s1, c1);
+                // half 0 slots: x, sin / cos of octaves 0 and 1; half 1: sin / cos of octaves 2 and 3
+                g[a] = half ? 4.0f * (gp[a] * c0 - gp[3 + a] * s0) + 8.0f * (gp[6 + a] * c1 - gp[9 + a] * s1)
+                            : gp[a] + (gp[3 + a] * c0 - gp[6 + a] * s0) + 2.0f * (gp[9 + a] * c1 - gp[12 + a] * s1);
+                g[a] *= scale;
+            }
+            {
+                float acc_in = x[0] + x[1] + x[2];
+#pragma unroll
+                for (int j = 0; j < NCH; ++j) acc_in += f[j];
+#pragma unroll
+                for (int a = 0; a < 3; ++a) g[a] += 0.0f * acc_in;
+            }
+#pragma unroll
+            for (int j = 0; j < NCH; ++j) {
+                const int q = 5 * j;
+                float s1, c1, s2, c2;
+                hw_sincos(f[j], s1, c1);
+                hw_sincos(2.0f * f[j], s2, c2);
+                const float df = gc[q >> 4][q & 15] + gc[(q + 1) >> 4][(q + 1) & 15] * c1 - gc[(q + 2) >> 4][(q + 2) & 15] * s1 +
+                                 2.0f * (gc[(q + 3) >> 4][(q + 3) & 15] * c2 - gc[(q + 4) >> 4][(q + 4) & 15] * s2);
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    const float jl = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(stash, jl_lane + (uint32_t)(3 * j + a) * 256u, 0, 0));
+                    g[a] = __builtin_fmaf(df, jl, g[a]);
+                }
+            }
+#pragma unroll
+            for (int a = 0; a < 3; ++a) g[a] += __shfl_xor(g[a], 32, 64);
+            if (half == 0 && live) {
+                sdf_out[src] = (s_val + b_last) * inv_scale;
+                grad_out[3 * src] = g[0] * inv_scale;
+                grad_out[3 * src + 1] = g[1] * inv_scale;
+                grad_out[3 * src + 2] = g[2] * inv_scale;
+            }
+        }
+        if (lane == 0) atomicExch(lock, 0u);
+    }
+#undef GB_BOUNDARY
+#undef GB_LOAD
+#undef GB_MFMA
+#undef GB_RACC
+#undef GB_TERM
+#undef GB_SEGMENT
+#undef GB_ZERO
+#undef GB_SOFTPLUS_TILE
+#undef GB_SPLIT_TILE
+}
+
+int gens_fill_levels(const char* who, LevelSet* ls, const float* const* data, const int* dims, int n_levels);
+
+extern "C" int gens_sdf_bf16x3_pieces(int n_levels) {
+    return n_levels == 3 ? GradShapeB<3>::NCHUNK * GB_CH : n_levels == 5 ? GradShapeB<5>::NCHUNK * GB_CH : 0;
+}
+
+extern "C" int64_t gens_sdf_grad_f16_stash_bytes(void);      // the stash is k6gh's: the same slots, the same layout
+
+static int check_bf16x3_args(const char* who, int n_levels, const void* pieces, const float* w_out, float scale, const float* pts, int64_t n,
+                             const float* sdf_out) {
+    GENS_CHECK_ARG(n_levels == 3 || n_levels == 5, GENS_ELIMIT, "%s: built for 3 or 5 volume levels, got %d", who, n_levels);
+    GENS_CHECK_ARG(pieces && w_out, GENS_EINVAL, "%s: null weight stream", who);
+    GENS_CHECK_ARG(((uintptr_t)pieces & 15) == 0, GENS_EINVAL, "%s: the weight stream must be 16-byte aligned", who);
+    GENS_CHECK_ARG(n >= 0 && (n == 0 || (pts && sdf_out)), GENS_EINVAL, "%s: null pts / output", who);
+    GENS_CHECK_ARG(scale != 0.0f, GENS_EINVAL, "%s: scale must be non-zero", who);
+    return 0;
+}
+
+extern "C" int gens_sdf_value_bf16x3(const float* const* vols_packed, const int* dims, int n_levels, const void* pieces, const float* w_out,
+                                     float b_last, float scale, const float* pts, const int64_t* index, int64_t n, const int32_t* n_device,
+                                     float* sdf_out, void* stream) {
+    LevelSet vs;
+    if (int e = gens_fill_levels("gens_sdf_value_bf16x3", &vs, vols_packed, dims, n_levels)) return e;
+    if (int e = check_bf16x3_args("gens_sdf_value_bf16x3", n_levels, pieces, w_out, scale, pts, n, sdf_out)) return e;
+    if (n == 0) return 0;
+    const unsigned grid = gens_blocks(n, 32 * GB_WAVES);
+    if (n_levels == 3)
+        sdf_bf16x3_k<3, false><<<grid, 64 * GB_WAVES, GB_W_BYTES, (hipStream_t)stream>>>(vs, (const char*)pieces, w_out, b_last, scale, 1.0f / scale, pts,
+                                                                                          index, n, n_device, sdf_out, nullptr, nullptr);
+    else
+        sdf_bf16x3_k<5, false><<<grid, 64 * GB_WAVES, GB_W_BYTES, (hipStream_t)stream>>>(vs, (const char*)pieces, w_out, b_last, scale, 1.0f / scale, pts,
+                                                                                          index, n, n_device, sdf_out, nullptr, nullptr);
+    return gens_launch_status("gens_sdf_value_bf16x3");
+}
+
+extern "C" int gens_sdf_grad_bf16x3(const float* const* vols_packed, const int* dims, int n_levels, const void* pieces, const float* w_out,
+                                    float b_last, float scale, const float* pts, const int64_t* index, int64_t n, const int32_t* n_device,
+                                    float* sdf_out, float* grad_out, void* stash, void* stream) {
+    LevelSet vs;
+    if (int e = gens_fill_levels("gens_sdf_grad_bf16x3", &vs, vols_packed, dims, n_levels)) return e;
+    if (int e = check_bf16x3_args("gens_sdf_grad_bf16x3", n_levels, pieces, w_out, scale, pts, n, sdf_out)) return e;
+    GENS_CHECK_ARG(n == 0 || grad_out, GENS_EINVAL, "gens_sdf_grad_bf16x3: null gradient output");
+    GENS_CHECK_ARG(stash && ((uintptr_t)stash & 15) == 0, GENS_EINVAL,
+                   "gens_sdf_grad_bf16x3: null or misaligned stash (gens_sdf_grad_f16_stash_bytes() bytes, zeroed once)");
+    GENS_CHECK_ARG(gens_sdf_grad_f16_stash_bytes() == (int64_t)GB_SLOTS * GB_SLOT_BYTES, GENS_EINVAL, "gens_sdf_grad_bf16x3: stash layout differs from k6gh's");
+    if (n == 0) return 0;
+    static GensLdsOptIn lds3, lds5;
+    if (int e = n_levels == 3 ? gens_lds_opt_in(lds3, (const void*)sdf_bf16x3_k<3, true>, GB_LDS_BYTES, "gens_sdf_grad_bf16x3")
+                              : gens_lds_opt_in(lds5, (const void*)sdf_bf16x3_k<5, true>, GB_LDS_BYTES, "gens_sdf_grad_bf16x3"))
+        return e;
+    const unsigned grid = gens_blocks(n, 32 * GB_WAVES);
+    if (n_levels == 3)
+        sdf_bf16x3_k<3, true><<<grid, 64 * GB_WAVES, GB_LDS_BYTES, (hipStream_t)stream>>>(vs, (const char*)pieces, w_out, b_last, scale, 1.0f / scale, pts,
+                                                                                           index, n, n_device, sdf_out, grad_out, (char*)stash);
+    else
+        sdf_bf16x3_k<5, true><<<grid, 64 * GB_WAVES, GB_LDS_BYTES, (hipStream_t)stream>>>(vs, (const char*)pieces, w_out, b_last, scale, 1.0f / scale, pts,
+                                                                                           index, n, n_device, sdf_out, grad_out, (char*)stash);
+    return gens_launch_status("gens_sdf_grad_bf16x3");
+}

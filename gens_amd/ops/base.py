@@ -19,7 +19,8 @@ class KernelChoice:
     """Which generation of a fused kernel an operator launches -- plain attributes, set once from the environment at import (the switches
     of INTEGRATION.md) and changed by assignment afterwards (tests: monkeypatch.setattr(ops.kernels, ...)).  The operators read these
     attributes; nothing on a launch path reads os.environ.
-        sdf_value / sdf_grad   "transposed" (k6t / k6g: register-chained, the default) | "rowmajor" (k6_sdfmlp.hip: cross-check, other shapes)
+        sdf_value / sdf_grad   "bf16x3" (k6b: three-term bfloat16 operands, float32-accurate; the default, 3 and 5 levels -- other level counts
+                               take "transposed") | "transposed" (k6t / k6g: float32 MFMA, register-chained) | "rowmajor" (k6_sdfmlp.hip: cross-check)
         blend                  "transposed" (k7t, two to four source views) | "rowmajor" (k7_blend.hip)
         blend_train_fwd        "transposed" (the training step's forward through k7t + gens_blend_pack_t) | "rowmajor" (k18's own forward)
         blend_train_wgrad      "inside" (the weight-gradient sums inside the backward launch, gens_blend_train_bwd_acc) | "rows" (operand rows + K14)
@@ -32,8 +33,9 @@ class KernelChoice:
         k2_bricks_min          points from which the stand-alone look-up's volume-gradient scatter runs brick by brick (gens_lookup_volume_bwd_bricks)"""
 
     def __init__(self, env=os.environ):
-        self.sdf_value = "rowmajor" if env.get("GENS_SDF_VALUE_ROWMAJOR") else "transposed"
-        self.sdf_grad = "rowmajor" if env.get("GENS_SDF_GRAD_ROWMAJOR") else "transposed"
+        f32_mfma = "transposed" if env.get("GENS_SDF_F32_MFMA") else "bf16x3"
+        self.sdf_value = "rowmajor" if env.get("GENS_SDF_VALUE_ROWMAJOR") else f32_mfma
+        self.sdf_grad = "rowmajor" if env.get("GENS_SDF_GRAD_ROWMAJOR") else f32_mfma
         self.sdf_grad_f16 = not env.get("GENS_SDF_GRAD_F32_ONLY")
         self.blend = "rowmajor" if env.get("GENS_BLEND_ROWMAJOR") else "transposed"
         self.blend_train_fwd = "rowmajor" if env.get("GENS_BLEND_TRAIN_ROWMAJOR") else "transposed"
@@ -80,7 +82,8 @@ _SDF_GRAD_F16_STASH = {}
 
 
 def sdf_grad_f16_stash(device):
-    """gens_sdf_grad_f16's (CU, wave)-private slots (softplus' of one layer and the trilinear Jacobians): one zeroed buffer per device."""
+    """gens_sdf_grad_f16's (CU, wave)-private slots (softplus' of one layer and the trilinear Jacobians): one zeroed buffer per device, shared
+    with gens_sdf_grad_bf16x3 (the same slot layout; the slots' lock words keep two kernels on two streams apart)."""
     key = torch.device(device).index if torch.device(device).index is not None else torch.cuda.current_device()
     buf = _SDF_GRAD_F16_STASH.get(key)
     if buf is None:

@@ -273,14 +273,16 @@ def _pack_grad_stream(ws, bs, n_levels):
     return stream, w_out
 
 
-def _pack_grad_pieces(ws, bs, n_levels, n_pieces=None):
+def _pack_grad_pieces(ws, bs, n_levels, n_pieces=None, terms=2):
     """The piece stream of gens_sdf_grad_f16 (k6gh_sdf_grad_f16.hip): 1 KB pieces = the A operand (hi or lo halfs) of one 32-row output
     tile and one 16-deep K block, lane (m, kh) holding row m's weights for the eight reduction slots of lane half kh (_value_slots).
     Forward: layer 0's two point-encoding K blocks, then per layer the conditioning K blocks, (layer 3: the point-encoding blocks,) the
     eight hidden blocks -- the scaling of _pack_value_units, 4 tiles x {hi, lo} per block.  Reverse, on the TRUE transposed matrices,
     layer 5 down to 1: per K block of G_l (layer 2: seven) the four hidden tiles, the conditioning tiles and at layer 3 the
     point-encoding tile, rows ordered as in _pack_grad_stream; then the eight blocks of G_0 for the point-encoding tile.  Padded with
-    zeros to whole chunks of eight pieces.  -> (pieces (N, 64, 8) float16, largest magnitude handed to half precision)."""
+    zeros to whole chunks of eight pieces.  -> (pieces (N, 64, 8) float16, largest magnitude handed to half precision).
+    terms=3: the stream of gens_sdf_value_bf16x3 / gens_sdf_grad_bf16x3 (k6b_sdf_bf16x3.hip) -- the same order with three round-to-nearest
+    bfloat16 terms (x0, x1, x2) per (block, tile) instead of (hi, lo): -> (pieces (N, 64, 8) bfloat16, largest magnitude)."""
     dev = ws[0].device
     c = 100.0 / math.log(2.0)
     r2 = 1.0 / math.sqrt(2.0)
@@ -351,12 +353,18 @@ def _pack_grad_pieces(ws, bs, n_levels, n_pieces=None):
     mat = slot_rows(w0, pe_flat, 1)
     rev.append(blocks(torch.cat([mat, zz.expand(32, 2)], 1), hid).reshape(-1, 64, 8))
     tiles = torch.cat([fwd] + rev, 0)                                             # one row per (block, tile)
-    hi = tiles.half()
-    lo = (tiles - hi.float()).half()
-    pieces = torch.stack([hi, lo], 1).reshape(-1, 64, 8)                          # [block][tile][hi, lo]
+    if terms == 3:
+        parts, rest = [], tiles
+        for _ in range(3):                                                        # x - x0 and x - x0 - x1 are exact in float32
+            parts.append(rest.bfloat16())
+            rest = rest - parts[-1].float()
+    else:
+        hi = tiles.half()
+        parts = [hi, (tiles - hi.float()).half()]
+    pieces = torch.stack(parts, 1).reshape(-1, 64, 8)                             # [block][tile][hi, lo] / [x0, x1, x2]
     pad = (-pieces.shape[0]) % 8 if n_pieces is None else n_pieces - pieces.shape[0]      # (whole chunks of the kernel's ring)
     if pad:
-        pieces = torch.cat([pieces, torch.zeros(pad, 64, 8, device=dev, dtype=torch.float16)], 0)
+        pieces = torch.cat([pieces, torch.zeros(pad, 64, 8, device=dev, dtype=pieces.dtype)], 0)
     return pieces.contiguous(), float(tiles.abs().max())
 
 
@@ -424,6 +432,12 @@ class SdfMlpPlan:
                 self.grad_scale = 2.0 ** min(14, max(-10, round(math.log2(256.0 / top)))) if top > 0 and math.isfinite(top) else 1.0
                 if not gvmax < 6.0e4:
                     self.grad_pieces = None
+            # the three-term bfloat16 kernels (k6b, generation "bf16x3" of the "f32" arithmetic): 3 and 5 levels, no range limit
+            self.bf16x3_pieces = None
+            n_pieces = L.load().gens_sdf_bf16x3_pieces(self.n_levels) if self.n_levels in (3, 5) else 0
+            if n_pieces:
+                self.bf16x3_pieces, _ = _pack_grad_pieces(ws, bs, self.n_levels, n_pieces, terms=3)
+                assert self.bf16x3_pieces.shape[0] == n_pieces
             self.overflow = torch.zeros(1, device=dev, dtype=torch.int32)
         self.wf_table, self.wb_table, self.bias_table = L.ptr_table(self.wf), L.ptr_table(self.wb), L.ptr_table(self.bias)
         self.key = SdfMlpPlan.version(net)
@@ -439,8 +453,10 @@ class SdfMlpPlan:
 def sdf_mlp(plan, volumes, pts, index=None, want_grad=False, sdf_out=None, grad_out=None, precision="f32", count=None):
     """sdf (and d sdf/dx) of pts[index] written to sdf_out[index] / grad_out[index] (fresh, densely indexed outputs if
     no buffers are given).  volumes: packed VolumeSet with 3 or 5 levels.  No autograd graph is built (inference).
-    precision: "f32" (exact float32 MFMA) or "f16x2" (split-half operands, ~1e-6 relative; check plan.overflowed()) -- value-only
-    launches on gens_sdf_value_f16, value + gradient launches on gens_sdf_grad_f16 (float32 if the weights leave the half range).
+    precision: "f32" (float32-accurate products: three-term bfloat16 operands on gens_sdf_value_bf16x3 / gens_sdf_grad_bf16x3 at 3 and 5
+    levels under kernels.sdf_value / sdf_grad "bf16x3", float32 MFMA otherwise) or "f16x2" (split-half operands, ~1e-6 relative; check
+    plan.overflowed()) -- value-only launches on gens_sdf_value_f16, value + gradient launches on gens_sdf_grad_f16 (the "f32" kernels if the
+    weights leave the half range or kernels.sdf_grad_f16 is off).
     count: optional (1,) int32 device tensor from compact_valid(): only the first `count` entries of `index` are evaluated."""
     assert isinstance(volumes, VolumeSet) and volumes.layout == L.LAYOUT_PACKED and volumes.n == plan.n_levels
     pts = _c(pts.detach().reshape(-1, 3).to(_f32))
@@ -465,8 +481,14 @@ def sdf_mlp(plan, volumes, pts, index=None, want_grad=False, sdf_out=None, grad_
                plan.scale, plan.grad_scale, L.ptr(pts), L.ptr(idx, torch.int64), n, L.ptr(count, torch.int32), L.ptr(sdf_out), L.ptr(grad_out),
                L.ptr(sdf_grad_f16_stash(pts.device), torch.uint8), L.ptr(plan.overflow, torch.int32), L.stream(),
                nbytes=nbytes, flops=n * flops, live=None if count is None else (count, n), label="gens_sdf_grad_f16")
-    elif want_grad and kernels.sdf_grad == "transposed":
-        # (under "f16x2" with weights out of the half range this pass stays float32)
+    elif want_grad and kernels.sdf_grad == "bf16x3" and getattr(plan, "bf16x3_pieces", None) is not None:
+        # (under "f16x2" with weights out of the half range this pass takes the "f32" kernel)
+        L.call("gens_sdf_grad_bf16x3", volumes.table, volumes.dim_table, volumes.n, L.ptr(plan.bf16x3_pieces, torch.bfloat16), L.ptr(plan.grad_row),
+               plan.b_last, plan.scale, L.ptr(pts), L.ptr(idx, torch.int64), n, L.ptr(count, torch.int32), L.ptr(sdf_out), L.ptr(grad_out),
+               L.ptr(sdf_grad_f16_stash(pts.device), torch.uint8), L.stream(),
+               nbytes=nbytes, flops=n * flops, live=None if count is None else (count, n), label="gens_sdf_grad_bf16x3")
+    elif want_grad and kernels.sdf_grad in ("transposed", "bf16x3"):
+        # (under "f16x2" with weights out of the half range this pass stays float32; "bf16x3" at level counts other than 3 and 5)
         L.call("gens_sdf_grad", volumes.table, volumes.dim_table, volumes.n, L.ptr(plan.grad_stream), L.ptr(plan.grad_row), plan.b_last,
                plan.scale, L.ptr(pts), L.ptr(idx, torch.int64), n, L.ptr(count, torch.int32), L.ptr(sdf_out), L.ptr(grad_out),
                L.ptr(sdf_grad_stash(pts.device), torch.uint8), L.stream(),
@@ -476,7 +498,11 @@ def sdf_mlp(plan, volumes, pts, index=None, want_grad=False, sdf_out=None, grad_
                plan.b_last, plan.scale, L.ptr(pts), L.ptr(idx, torch.int64), n, L.ptr(count, torch.int32), L.ptr(sdf_out),
                L.ptr(plan.overflow, torch.int32), L.stream(), nbytes=nbytes, flops=n * flops, live=None if count is None else (count, n),
                label="gens_sdf_value_f16")
-    elif not want_grad and kernels.sdf_value == "transposed":
+    elif not want_grad and kernels.sdf_value == "bf16x3" and getattr(plan, "bf16x3_pieces", None) is not None:
+        L.call("gens_sdf_value_bf16x3", volumes.table, volumes.dim_table, volumes.n, L.ptr(plan.bf16x3_pieces, torch.bfloat16), L.ptr(plan.grad_row),
+               plan.b_last, plan.scale, L.ptr(pts), L.ptr(idx, torch.int64), n, L.ptr(count, torch.int32), L.ptr(sdf_out), L.stream(),
+               nbytes=nbytes, flops=n * flops, live=None if count is None else (count, n), label="gens_sdf_value_bf16x3")
+    elif not want_grad and kernels.sdf_value in ("transposed", "bf16x3"):
         L.call("gens_sdf_value", volumes.table, volumes.dim_table, volumes.n, L.ptr(plan.value_stream), L.ptr(plan.value_row), plan.b_last,
                plan.scale, L.ptr(pts), L.ptr(idx, torch.int64), n, L.ptr(count, torch.int32), L.ptr(sdf_out), L.stream(), nbytes=nbytes,
                flops=n * flops, live=None if count is None else (count, n), label="gens_sdf_value")

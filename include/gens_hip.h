@@ -370,6 +370,24 @@ int gens_sdf_grad_f16_stash_reset(void* stash, void* stream);      /* as gens_sd
 /* number of 1 KB pieces in the weight stream of gens_sdf_grad_f16, padding included (0 = unsupported level count) */
 int gens_sdf_grad_f16_pieces(int n_levels);
 
+/* The same network with float32-accurate products on the bf16 matrix cores (k6b_sdf_bf16x3.hip): every float32 operand is split into
+ * THREE round-to-nearest bfloat16 terms x0 + x1 + x2 and a product is x2 y0 + x1 y1 + x0 y2 + x1 y0 + x0 y1 + x0 y0 with float32
+ * accumulation (the dropped terms are below ~2^-26 relative); bfloat16 has float32's exponent range, so there is no overflow flag.  The
+ * dataflow of gens_sdf_grad_f16.  Three or five volume levels; GENS_ELIMIT otherwise.  gens_sdf_value_bf16x3 runs the forward half of
+ * gens_sdf_grad_bf16x3's code on the forward prefix of the same stream: the two return the same float32 sdf for the same point.
+ *   pieces: DEVICE, 16-byte aligned, gens_sdf_bf16x3_pieces(n_levels) x 1024 bytes in the order of gens_amd.ops._pack_grad_pieces(terms=3):
+ *   [64 lanes][8 bfloat16] per (K block, output tile, x0 | x1 | x2).
+ *   w_out: the output row of gens_sdf_grad (same layout).
+ *   stash: gens_sdf_grad_f16's (gens_sdf_grad_f16_stash_bytes() bytes, zeroed once; the same buffer may serve both kernels). */
+int gens_sdf_value_bf16x3(const float* const* vols_packed, const int* dims, int n_levels, const void* pieces, const float* w_out,
+                          float b_last, float scale, const float* pts, const int64_t* index, int64_t n, const int32_t* n_device,
+                          float* sdf_out, void* stream);
+int gens_sdf_grad_bf16x3(const float* const* vols_packed, const int* dims, int n_levels, const void* pieces, const float* w_out,
+                         float b_last, float scale, const float* pts, const int64_t* index, int64_t n, const int32_t* n_device,
+                         float* sdf_out, float* grad_out, void* stash, void* stream);
+/* number of 1 KB pieces in the weight stream of gens_sdf_value_bf16x3 / gens_sdf_grad_bf16x3, padding included (0 = unsupported level count) */
+int gens_sdf_bf16x3_pieces(int n_levels);
+
 /* ------------------------------------------------------------------------------------------------------------
  * K21  depth-wise 2-D convolutions of the MnasNet trunk (k21_depthwise.hip): nn.Conv2d(c, c, k, padding = k / 2, stride, groups = c,
  *      bias = False) with k in {3, 5}, stride in {1, 2} -- torchvision's MNASNet layers used by feature_network_mnasnet.py:53-103 -- for which
