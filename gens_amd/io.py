@@ -4,9 +4,9 @@
     val_img/…png, val_normal/…png          rendered colour and normal images                                      (runner.py:243-244)
     val_render_depth/…png, val_sdf_depth/… depth maps through the magma colour map, fixed range [0, 2.5]          (runner.py:245-246, 379-392)
 
-and the mask-based mesh cleaning of utils/clean_mesh.py:9-35 (drop faces with a vertex that fewer than two source masks see).
-The ray-casting step of the reference's cleaning (clean_mesh_outside_frustum, utils/clean_mesh.py:38-99: pyembree through
-trimesh) is not rebuilt; its tail, the removal of small connected components (:101-106), is `drop_small_components`."""
+and the reference's mesh cleaning (utils/clean_mesh.py): the mask half (:9-35, drop faces with a vertex that fewer than two source masks
+see) on the host, the ray-cast half (clean_mesh_outside_frustum, :38-106: pyembree through trimesh, then trimesh's face components) on the
+device (K23), and the chain of both (`clean_mesh`, :109-130).  `drop_small_components` is a host restatement of the component step."""
 import os
 
 import numpy as np
@@ -88,8 +88,10 @@ def clean_mesh_by_mask(vertices, triangles, masks, intrs, c2ws, min_nb_visible=1
 
 
 def drop_small_components(vertices, triangles, min_faces=500):
-    """utils/clean_mesh.py:101-106 without trimesh: keep the connected components (faces sharing an edge) of at least `min_faces`
-    faces and drop the vertices nothing references any more -> (vertices, triangles) re-indexed."""
+    """utils/clean_mesh.py:101-106 without trimesh, on the host: keep the connected components (faces sharing an edge) of at least
+    `min_faces` faces and drop the vertices nothing references any more -> (vertices, triangles) re-indexed.  Faces are joined across
+    every shared edge, also one that more than two faces share; trimesh's face_adjacency (and clean_mesh_outside_frustum) joins only
+    across edges of exactly two faces.  On manifold meshes the two agree."""
     from scipy.sparse import coo_matrix
     from scipy.sparse.csgraph import connected_components
     tri = np.asarray(triangles, dtype=np.int64).reshape(-1, 3)
@@ -110,6 +112,88 @@ def drop_small_components(vertices, triangles, min_faces=500):
     used[tri.reshape(-1)] = True
     remap = np.cumsum(used) - 1
     return v[used], remap[tri].astype(np.asarray(triangles).dtype if len(tri) else np.int64)
+
+
+def _as_numpy(x):
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+def _device_of(*xs):
+    for x in xs:
+        if isinstance(x, torch.Tensor) and x.is_cuda:
+            return x.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+@torch.no_grad()
+def clean_mesh_outside_frustum(vertices, triangles, masks, intrs, c2ws, upscale=4, min_faces=500):
+    """utils/clean_mesh.py:38-106 on the device (K23): keep the faces that some masked pixel of some view (upsampled by `upscale`) sees
+    first, then the connected components of at least `min_faces` faces, then the referenced vertices (in their order, as trimesh's
+    remove_unreferenced_vertices).  vertices (V,3), triangles (F,3) (arrays or tensors), masks (nv,H,W) raw (a pixel casts iff its
+    nearest-upsampled value is > 0), intrs / c2ws (nv,4,4) -> (vertices, triangles) as numpy arrays of the inputs' dtypes.
+
+    Faithful to the reference's quirks: the sorted list of hit faces has its first entry dropped (`values[1:]`) -- that is the -1 of the
+    misses when some masked ray missed, and otherwise the smallest face index hit; a face is seen if one view sees it (num_com_vis = 1);
+    components come from trimesh's face_adjacency (edges shared by exactly two faces), and a face without such a neighbour is in no
+    component at all (trimesh takes the graph's nodes from its edges).  One deliberate deviation: where no component survives, the
+    reference raises inside np.concatenate([]); this returns an empty mesh.  trimesh also merges coincident vertices when it loads a
+    mesh; K12 emits one vertex per lattice edge, so vertices coincide only where a lattice value equals the threshold exactly, and no
+    merge is done here."""
+    from . import ops
+    v_np, t_np = _as_numpy(vertices), _as_numpy(triangles)
+    dev = _device_of(vertices, triangles, masks)
+    v = torch.as_tensor(v_np, dtype=torch.float64).reshape(-1, 3).to(dev)
+    t = torch.as_tensor(t_np.astype(np.int64)).reshape(-1, 3).to(dev)
+    if len(t):
+        grid = ops.build_mesh_grid(v, t)
+        flags, any_miss = ops.visible_faces(grid, masks, intrs, c2ws, upscale)
+        seen = flags.bool()
+        if not bool(any_miss.item()):                   # values[1:] drops the smallest hit face instead of the -1 of the misses
+            hit = torch.nonzero(seen).reshape(-1)
+            if len(hit):
+                seen[hit[0]] = False
+        t = t[seen]
+    return _large_components(v_np, t_np.dtype, t, min_faces)
+
+
+def _large_components(v_np, t_dtype, t, min_faces):
+    """The tail of clean_mesh_outside_frustum (clean_mesh.py:101-106) on device triangles t (F,3) int64."""
+    from . import ops
+    dev, n_v = t.device, len(v_np)
+    if len(t):
+        pairs = ops.face_adjacency(t, n_v)
+        label = ops.face_components(t, n_v, pairs).long()
+        in_graph = torch.zeros(len(t), device=dev, dtype=torch.bool)
+        in_graph[pairs.reshape(-1).long()] = True
+        t = t[in_graph & (torch.bincount(label, minlength=len(t))[label] >= min_faces)]
+    used = torch.zeros(n_v, device=dev, dtype=torch.bool)
+    used[t.reshape(-1)] = True
+    remap = torch.cumsum(used, 0) - 1
+    return v_np.reshape(-1, 3)[used.cpu().numpy()], remap[t].cpu().numpy().astype(t_dtype)
+
+
+@torch.no_grad()
+def _drop_small_components_device(vertices, triangles, min_faces=500):
+    """clean_mesh.py:101-106 on the device (K23), trimesh's rule: faces are joined across edges of exactly two faces, and a face without
+    such a neighbour is in no component -> (vertices, triangles) numpy, unreferenced vertices removed in their order.  Equal to
+    `drop_small_components` on manifold meshes (for min_faces >= 2)."""
+    v_np, t_np = _as_numpy(vertices), _as_numpy(triangles)
+    dev = _device_of(vertices, triangles)
+    return _large_components(v_np, t_np.dtype, torch.as_tensor(t_np.astype(np.int64)).reshape(-1, 3).to(dev), min_faces)
+
+
+@torch.no_grad()
+def clean_mesh(vertices, triangles, masks, intrs, c2ws, dilation_radius=11, min_nb_visible=1, upscale=2, min_faces=500):
+    """utils/clean_mesh.py:109-130: masks (nv,H,W[,3]) are averaged over a trailing channel axis; the faces outside the dilated (> 0.5)
+    masks go (clean_mesh_by_mask, on the host), then clean_mesh_outside_frustum runs with the un-dilated averaged masks -> (vertices,
+    triangles) numpy, unreferenced vertices removed (see clean_mesh_outside_frustum for the quirks kept and the one deviation).
+    min_faces: the component size of clean_mesh.py:102 (500 there, not an argument of the reference's clean_mesh)."""
+    masks = masks.detach().cpu()
+    if masks.dim() > 3:
+        masks = masks.mean(dim=-1)
+    v_np = _as_numpy(vertices)
+    kept = clean_mesh_by_mask(v_np, _as_numpy(triangles), dilate_masks(masks, dilation_radius), intrs, c2ws, min_nb_visible)
+    return clean_mesh_outside_frustum(v_np, kept, masks, intrs, c2ws, upscale=upscale, min_faces=min_faces)
 
 
 def dilate_masks(masks, radius=11):
@@ -136,13 +220,20 @@ def save_depth(depth, file_path):
     Image.fromarray(depth_to_rgb(depth)).save(file_path)
 
 
-def save_validation_outputs(base_exp_dir, outputs, inputs, tag, image_tag=None, clean=False):
+def save_validation_outputs(base_exp_dir, outputs, inputs, tag, image_tag=None, clean=False, clean_frustum=False):
     """Store one validated view the way runner.py:215-246 (tag = "epoch{e}", image names from inputs["file_name"]) and
-    runner.py:349-375 (tag = "step{s}", image_tag = the view index) do.  Returns the written paths."""
+    runner.py:349-375 (tag = "step{s}", image_tag = the view index) do.  Returns the written paths.
+    clean=True: the mask half of the cleaning only; clean=True, clean_frustum=True: the whole of utils/clean_mesh.py's clean_mesh
+    (`clean_mesh`, what runner.py --clean_mesh scores).  clean_frustum=True without clean=True is an error (the frustum step runs on
+    the mask half's result)."""
+    if clean_frustum and not clean:
+        raise ValueError("save_validation_outputs: clean_frustum=True needs clean=True")
     scene = inputs["scene"]
     image_tag = inputs["file_name"] if image_tag is None else image_tag
     vertices, triangles = outputs["vertices"], outputs["triangles"]
-    if clean:
+    if clean and clean_frustum:
+        vertices, triangles = clean_mesh(vertices, triangles, inputs["masks"], inputs["intrs"], inputs["c2ws"])
+    elif clean:
         triangles = clean_mesh_by_mask(vertices, triangles, dilate_masks(inputs["masks"]), inputs["intrs"], inputs["c2ws"])
     vertices = transform_vertices(vertices, inputs["scale_mat"].detach().cpu().numpy())
     paths = {}

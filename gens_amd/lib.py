@@ -48,6 +48,11 @@ class CompositeGrad(C.Structure):
                                   "g_smooth_error", "finish")]
 
 
+class MeshGridArgs(C.Structure):       # gens_mesh_grid (K23)
+    _fields_ = [(n, _p) for n in ("vertices", "triangles", "cell_start", "cell_faces")] + [("n_faces", _l)] + [
+        (n, _f) for n in ("lo_x", "lo_y", "lo_z", "cell")] + [(n, _i) for n in ("nx", "ny", "nz")]
+
+
 # name -> argtypes, mirroring include/gens_hip.h declaration by declaration
 SIGNATURES = {
     "gens_pack_nchw": [_p, _p, _i, _i, _i, _i, _p],
@@ -162,6 +167,12 @@ SIGNATURES = {
     "gens_tv_levels_blocks": [_ip, _i],
     "gens_tv_levels_fwd": [_pp, _pp, _ip, _i, _p, _p, _p],
     "gens_tv_levels_bwd": [_pp, _pp, _ip, _i, _p, _p, _pp, _p],
+    "gens_mesh_grid_count": [C.POINTER(MeshGridArgs), _p, _p],
+    "gens_mesh_grid_fill": [C.POINTER(MeshGridArgs), _p, _p],
+    "gens_ray_first_hit": [C.POINTER(MeshGridArgs), _p, _p, _l, _p, _p, _p],
+    "gens_view_rays_hit_faces": [C.POINTER(MeshGridArgs), _p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p],
+    "gens_face_cc_hook": [_p, _l, _p, _l, _p],
+    "gens_face_cc_compress": [_p, _l, _p, _p],
 }
 
 _lib = None

@@ -1,4 +1,4 @@
-"""K11 (lattice points) and K12 (iso-surface extraction on the device).
+"""K11 (lattice points), K12 (iso-surface extraction on the device) and K23 (ray casting against the extracted mesh, face components).
 
 Part of gens_amd.ops (see ops/__init__.py); citations are relative to /root/reference."""
 from .base import *  # noqa: F401,F403
@@ -51,6 +51,158 @@ def marching_cubes(u, threshold=0.0):
            L.ptr(triangles, i32) if nt else L.ptr(torch.empty(1, 3, device=dev, dtype=i32), i32), L.stream(),
            nbytes=total * 15 + nv * 24 + nt * 12)
     return vertices, triangles
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# K23  first hits against a triangle mesh and its face components (utils/clean_mesh.py:38-106: pyembree's intersects_first, trimesh's
+#      face_adjacency + connected_components)
+# ------------------------------------------------------------------------------------------------------------------
+class MeshGrid:
+    """A triangle mesh on the device with the uniform grid of K23 over it: about two cubic cells per face (at most 512 per axis), every
+    face listed in every cell its closed AABB overlaps.  vertices (V,3) float64, triangles (F,3) int32, cell_start (cells + 1) int32,
+    cell_faces int32; box = (lo_x, lo_y, lo_z, cell edge) float32, dims = (nx, ny, nz)."""
+
+    def __init__(self, vertices, triangles, cell_start, cell_faces, box, dims):
+        self.vertices, self.triangles, self.cell_start, self.cell_faces = vertices, triangles, cell_start, cell_faces
+        self.box, self.dims = tuple(float(b) for b in box), tuple(int(d) for d in dims)
+
+    @property
+    def n_faces(self):
+        return self.triangles.shape[0]
+
+    def args(self):
+        i32 = torch.int32
+        return L.MeshGridArgs(L.ptr(self.vertices, torch.float64), L.ptr(self.triangles, i32), L.ptr(self.cell_start, i32),
+                              L.ptr(self.cell_faces, i32), self.n_faces, *self.box, *self.dims)
+
+
+def _grid_box(vmin, vmax, n_faces):
+    """Box and cell count of the grid: the referenced vertices' bounding box padded by 1e-4 of its extent (float32 corner at or below it),
+    cubic cells of volume (box volume) / (2 F), at most 512 per axis -> ((lo_x, lo_y, lo_z, cell) float32 values, (nx, ny, nz))."""
+    import numpy as np
+    vmin, vmax = np.asarray(vmin, dtype=np.float64), np.asarray(vmax, dtype=np.float64)
+    ext = float((vmax - vmin).max())
+    scale = max(float(np.abs(vmin).max()), float(np.abs(vmax).max()), ext, 1e-30)
+    pad = 1e-4 * ext + 1e-6 * scale
+    lo = (vmin - pad).astype(np.float32)
+    span = (vmax + pad) - lo.astype(np.float64)
+    full = np.maximum(span, 1e-3 * span.max())
+    cell = (float(np.prod(full)) / (2.0 * max(n_faces, 1))) ** (1.0 / 3.0)
+    cell = max(cell, float(span.max()) / 512.0 * (1.0 + 1e-6))
+    c32 = np.float32(cell)
+    if float(c32) < cell:
+        c32 = np.nextafter(c32, np.float32(np.inf))
+    dims = np.clip(np.ceil(span / float(c32) * (1.0 + 1e-9)), 1, 512).astype(int)
+    return (float(lo[0]), float(lo[1]), float(lo[2]), float(c32)), tuple(int(d) for d in dims)
+
+
+def build_mesh_grid(vertices, triangles):
+    """vertices (V,3), triangles (F,3) device tensors -> MeshGrid (counting sort: count, exclusive scan, fill)."""
+    dev = vertices.device
+    v = _c(vertices.detach().to(torch.float64)).reshape(-1, 3)
+    t = _c(triangles.detach().to(device=dev, dtype=torch.int32)).reshape(-1, 3)
+    nf = t.shape[0]
+    if nf:
+        lim = torch.stack([t.min(), t.max()]).cpu()
+        if int(lim[0]) < 0 or int(lim[1]) >= v.shape[0]:
+            raise ValueError("build_mesh_grid: triangle index out of range")
+        used = v[t.reshape(-1).long()]
+        ext = torch.stack([used.amin(0), used.amax(0)]).cpu().numpy()
+        if not (abs(ext) < float("inf")).all():
+            raise ValueError("build_mesh_grid: non-finite vertex")
+        box, dims = _grid_box(ext[0], ext[1], nf)
+    else:
+        box, dims = (0.0, 0.0, 0.0, 1.0), (1, 1, 1)
+    cells = dims[0] * dims[1] * dims[2]
+    i32 = torch.int32
+    counts = torch.zeros(cells, device=dev, dtype=i32)
+    grid = MeshGrid(v, t, torch.zeros(cells + 1, device=dev, dtype=i32), torch.zeros(1, device=dev, dtype=i32), box, dims)
+    if nf == 0:
+        return grid
+    L.call("gens_mesh_grid_count", C.byref(grid.args()), L.ptr(counts, i32), L.stream())
+    ends = torch.cumsum(counts, 0, dtype=torch.int64)
+    total = int(ends[-1])
+    if total >= 2 ** 31:
+        raise RuntimeError(f"build_mesh_grid: {total} face-cell overlaps exceed int32")
+    grid.cell_start[1:] = ends.to(i32)
+    grid.cell_faces = torch.empty(max(total, 1), device=dev, dtype=i32)
+    counts.zero_()                              # (now the fill's cursor)
+    L.call("gens_mesh_grid_fill", C.byref(grid.args()), L.ptr(counts, i32), L.stream())
+    return grid
+
+
+def ray_mesh_first_hit(rays_o, rays_d, grid):
+    """trimesh's intersects_first: rays (N,3) -> (face (N,) int32, -1 on a miss; t (N,) float32 along rays_d, +inf on a miss).  The first
+    hit is the smallest (t, face) over the faces hit at t > 0 from either side (watertight test in float64)."""
+    ro = _c(rays_o.detach().to(_f32)).reshape(-1, 3)
+    rd = _c(rays_d.detach().to(_f32)).reshape(-1, 3)
+    n = ro.shape[0]
+    face = torch.empty(n, device=ro.device, dtype=torch.int32)
+    t = torch.empty(n, device=ro.device, dtype=_f32)
+    L.call("gens_ray_first_hit", C.byref(grid.args()), L.ptr(ro), L.ptr(rd), n, L.ptr(face, torch.int32), L.ptr(t), L.stream())
+    return face, t
+
+
+def view_ray_cams(intrs, c2ws):
+    """(nv,4,4) intrinsics and camera-to-world -> (nv,21) float32 on the host: K^-1[:3,:3] (torch.inverse of each float32 4x4 on the CPU, as
+    clean_mesh.py:60 takes it) and c2w[:3,:4]."""
+    intrs, c2ws = intrs.detach().cpu().float(), c2ws.detach().cpu().float()
+    return torch.stack([torch.cat([intrs[i].inverse()[:3, :3].reshape(-1), c2ws[i][:3, :4].reshape(-1)]) for i in range(intrs.shape[0])])
+
+
+def visible_faces(grid, masks, intrs, c2ws, upscale):
+    """The first-hit half of clean_mesh_outside_frustum (clean_mesh.py:45-78) in one launch: every pixel of every view upsampled by
+    `upscale` whose nearest-upsampled mask is > 0 casts the ray clean_mesh.py:50-66 builds.  masks (nv,H,W) (the raw, view-averaged masks),
+    intrs / c2ws (nv,4,4) -> (flags (F,) uint8: 1 for every face some ray hits first, any_miss (1,) int32: 1 if some cast ray missed)."""
+    dev = grid.vertices.device
+    m = _c(masks.detach().to(device=dev, dtype=_f32))
+    nv, h, w = m.shape
+    cams = view_ray_cams(intrs, c2ws).to(dev)
+    hu, wu = int(h * upscale), int(w * upscale)
+    inv_scale = float(torch.tensor(1.0 / upscale, dtype=torch.float32))
+    flags = torch.zeros(max(grid.n_faces, 1), device=dev, dtype=torch.uint8)
+    any_miss = torch.zeros(1, device=dev, dtype=torch.int32)
+    L.call("gens_view_rays_hit_faces", C.byref(grid.args()), L.ptr(m), L.ptr(cams), nv, h, w, hu, wu, inv_scale, L.ptr(flags, torch.uint8),
+           L.ptr(any_miss, torch.int32), L.stream())
+    return flags[:grid.n_faces], any_miss
+
+
+def face_adjacency(triangles, n_vertices):
+    """trimesh's face_adjacency: the pairs (P,2) int32 of faces that share an edge used by EXACTLY two faces (group_rows(edges,
+    require_count=2)), without the pairs of a face with itself (a face with a repeated vertex, [a, a, b], uses its edge (a, b) twice;
+    trimesh drops those pairs too); edge key min(v) * V + max(v), sorted by torch.sort."""
+    t = triangles.detach().reshape(-1, 3).to(torch.int64)
+    if t.shape[0] == 0:
+        return torch.zeros(0, 2, device=t.device, dtype=torch.int32)
+    e = torch.stack([t[:, [0, 1]], t[:, [1, 2]], t[:, [2, 0]]], 1).reshape(-1, 2)
+    key = torch.minimum(e[:, 0], e[:, 1]) * int(n_vertices) + torch.maximum(e[:, 0], e[:, 1])
+    key, order = torch.sort(key)
+    face = order // 3
+    same = key[1:] == key[:-1]
+    no = torch.zeros(1, device=t.device, dtype=torch.bool)
+    first = same & ~torch.cat([no, same[:-1]]) & ~torch.cat([same[1:], no])      # runs of length exactly two start here
+    i = torch.nonzero(first).reshape(-1)
+    i = i[face[i] != face[i + 1]]
+    return _c(torch.stack([face[i], face[i + 1]], 1).to(torch.int32))
+
+
+def face_components(triangles, n_vertices, pairs=None):
+    """Connected components of the face-adjacency graph (face_adjacency's pairs) -> labels (F,) int32 = the smallest face index of each
+    face's component.  Union-find on the device: a hook launch, then a compress launch."""
+    dev = triangles.device
+    nf = triangles.reshape(-1, 3).shape[0]
+    if pairs is None:
+        pairs = face_adjacency(triangles, n_vertices)
+    i32 = torch.int32
+    parent = torch.arange(nf, device=dev, dtype=i32)
+    label = torch.empty(nf, device=dev, dtype=i32)
+    if nf == 0:
+        return label
+    pairs = _c(pairs.to(i32))
+    if pairs.shape[0]:
+        L.call("gens_face_cc_hook", L.ptr(pairs, i32), pairs.shape[0], L.ptr(parent, i32), nf, L.stream())
+    L.call("gens_face_cc_compress", L.ptr(parent, i32), nf, L.ptr(label, i32), L.stream())
+    return label
 
 
 __all__ = [n_ for n_ in dir() if not n_.startswith("__")]      # private helpers travel too: the package namespace is the old module's

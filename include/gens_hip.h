@@ -54,7 +54,9 @@ const char* gens_last_error(void);
  *       wave per 16 rows, nothing shared between waves but the weights in LDS).
  *   12 = round 6: gens_upsample2d_cat (the warp features in one launch), gens_volume_build_levels_bits (the volume build leaves the masks as bits
  *       too), gens_select_views (the views of a fine-tune step out of the frozen maps and their layouts in one launch),
- *       gens_lookup_volume_bwd_bricks / _bwd2_bricks + gens_lookup_scatter_bricks_scratch_bytes (K2's volume-gradient scatter brick by brick). */
+ *       gens_lookup_volume_bwd_bricks / _bwd2_bricks + gens_lookup_scatter_bricks_scratch_bytes (K2's volume-gradient scatter brick by brick).
+ *       Later additions that change no existing entry keep 12: gens_sdf_{value,grad}_bf16x3 + gens_sdf_bf16x3_pieces, and K23's
+ *       gens_mesh_grid_{count,fill}, gens_ray_first_hit, gens_view_rays_hit_faces, gens_face_cc_{hook,compress}. */
 int gens_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -663,6 +665,44 @@ int gens_tv_bwd_scaled(const float* vol, const float* mask, int x, int y, int z,
  * ---------------------------------------------------------------------------------------------------------- */
 int gens_lattice_points(const float* bmin3_host, const float* bmax3_host, int res, int64_t first, int64_t count,
                         float* pts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * K23  the ray-cast half of the validation-mesh cleaning: replaces clean_mesh_outside_frustum (utils/clean_mesh.py:38-106),
+ *      pyembree's intersects_first through trimesh and trimesh's face-adjacency components
+ *   gens_mesh_grid (HOST struct, device pointers inside): a uniform grid of nx * ny * nz cubic cells of edge `cell` from (lo_x, lo_y, lo_z)
+ *     over a triangle mesh; vertices (V, 3) float64, triangles (n_faces, 3) int32 (indices < V: the caller's check); cell_start
+ *     (cells + 1) int32 = exclusive scan of gens_mesh_grid_count's counts; cell_faces (cell_start[cells]) int32 face ids, cell by cell.
+ *     1 .. 512 cells per axis; the box must hold every vertex.
+ *   gens_mesh_grid_count: counts (cells) int32, ACCUMULATES: per cell the faces whose closed AABB (widened by 1e-5 cells) overlaps it.
+ *   gens_mesh_grid_fill: writes cell_faces (any order inside a cell); cursor (cells) int32 zero-filled scratch.
+ *   gens_ray_first_hit: rays (n_rays, 3) float32 origins / directions -> face (n_rays) int32 (-1: miss) and t (n_rays) float32 (+inf: miss,
+ *     in units of |d|): the lexicographically smallest (t, face) over the faces hit at t > 0 from either side, watertight (Woop, Benthin,
+ *     Wald 2013, in float64).
+ *   gens_view_rays_hit_faces: the rays of clean_mesh.py:50-66 for the hu x wu upsampled pixels of nv views (hu = int(h * upscale)),
+ *     generated in the kernel; a pixel casts iff masks (nv, h, w) float32 at its nearest source pixel (F.interpolate's rule with
+ *     inv_scale = (float)(1 / upscale)) is > 0.  cams (nv, 21) float32: K^-1[:3, :3] row-major, then c2w[:3, :4] row-major.
+ *     flags (n_faces) uint8 and any_miss (1) int32 ACCUMULATE: 1 for every face some ray hits first, 1 if some cast ray misses.
+ *   gens_face_cc_hook: union-find over pairs (n_pairs, 2) int32 face ids; parent (n_faces) int32 starts as 0 .. n_faces - 1 and is updated
+ *     in place (larger roots hooked under smaller ones).  gens_face_cc_compress: label (n_faces) int32 = the root of every face = the
+ *     smallest face index of its component.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    const double* vertices;
+    const int32_t* triangles;
+    const int32_t* cell_start;
+    int32_t* cell_faces;
+    int64_t n_faces;
+    float lo_x, lo_y, lo_z, cell;
+    int nx, ny, nz;
+} gens_mesh_grid;
+int gens_mesh_grid_count(const gens_mesh_grid* grid, int32_t* counts, void* stream);
+int gens_mesh_grid_fill(const gens_mesh_grid* grid, int32_t* cursor, void* stream);
+int gens_ray_first_hit(const gens_mesh_grid* grid, const float* rays_o, const float* rays_d, int64_t n_rays, int32_t* face, float* t,
+                       void* stream);
+int gens_view_rays_hit_faces(const gens_mesh_grid* grid, const float* masks, const float* cams, int nv, int h, int w, int hu, int wu,
+                             float inv_scale, uint8_t* flags, int32_t* any_miss, void* stream);
+int gens_face_cc_hook(const int32_t* pairs, int64_t n_pairs, int32_t* parent, int64_t n_faces, void* stream);
+int gens_face_cc_compress(const int32_t* parent, int64_t n_faces, int32_t* label, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K14  C (m x n) = A^T B for tall row-major operands A (k x m), B (k x n), k >> m, n: the weight-gradient product of the training
