@@ -360,8 +360,8 @@ __global__ __launch_bounds__(256) void select_views_k(ViewSelect S, const int64_
         const int64_t j = i / q, r = i - j * q;
         int64_t v = index[j];
         v = v < 0 ? v + S.n_views[k] : v;                                             // (torch's negative indices)
-        if (v < 0 || v >= S.n_views[k]) continue;                                     // (an index torch would have refused: the view is left as it is)
-        dst[i] = src[v * q + r];
+        // an index torch would have refused: the row is NaN, never what the buffer held (no host check: the step is captured into graphs)
+        dst[i] = (v < 0 || v >= S.n_views[k]) ? make_float4(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), __builtin_nanf("")) : src[v * q + r];
     }
 }
 

@@ -144,13 +144,20 @@ class GenS(nn.Module):
     def _view_index_of(self, view_ids):
         """(gens.py:151-153: `self.features[i][view_ids]` with a Python list builds an index tensor on the host and copies it over -- every step, a
         pageable host-to-device copy, and not capturable into a graph: the index tensor is kept per list of ids; one gather serves both uses,
-        the reference's two copies hold the same values)"""
-        if torch.is_tensor(view_ids):
+        the reference's two copies hold the same values).  Ids from the host are checked once, when their index is built: one outside [-n, n) raises
+        IndexError as `features[i][view_ids]` does, and a negative one is mapped to n + id.  A device tensor is passed on unchecked (no host
+        synchronisation inside a captured step): the selection kernel fills the row of an out-of-range id with NaN."""
+        if torch.is_tensor(view_ids) and view_ids.device.type != "cpu":
             return view_ids
-        ids = tuple(int(v) for v in view_ids)
+        ids = tuple(int(v) for v in (view_ids.reshape(-1).tolist() if torch.is_tensor(view_ids) else view_ids))
+        n = int(self.features[0].shape[0])
         cache = getattr(self, "_view_index", None)
-        if cache is None or cache[0] != ids or cache[1].device != self.features[0].device:
-            cache = self._view_index = (ids, torch.tensor(ids, dtype=torch.long, device=self.features[0].device))
+        if cache is None or cache[0] != (ids, n) or cache[1].device != self.features[0].device:
+            for v in ids:
+                if not -n <= v < n:
+                    raise IndexError(f"view id {v} is out of range for {n} views")
+            index = torch.tensor([v + n if v < 0 else v for v in ids], dtype=torch.long, device=self.features[0].device)
+            cache = self._view_index = ((ids, n), index)
         return cache[1]
 
     def _seed_frozen_layouts(self, selected, index):

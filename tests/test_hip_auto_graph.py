@@ -229,6 +229,69 @@ def test_the_views_of_a_step_come_out_of_the_frozen_maps_and_their_layouts_in_on
             assert key == tuple((id(f), f._version) for f in got[:3]) and all(a is b for a, b in zip(kept, got[1:3]))
 
 
+def test_view_ids_out_of_range_raise_before_any_launch():
+    """`features[i][view_ids]` raises for an id outside [-n, n): so does the step, for a list or a CPU tensor of ids, before it launches anything."""
+    from gens_amd import lib as L
+    model = _finetune_model(False)
+    nv = model.features[0].shape[0]
+    for bad in ([0, nv], [-nv - 1, 1], torch.tensor([nv + 3, 0])):
+        ipts = _step_inputs(0)
+        ipts["view_ids"] = bad
+        model._view_index = None
+        L.profile_begin()
+        with pytest.raises(IndexError):
+            model("train", ipts, cos_anneal_ratio=1.0)
+        assert L.profile_end(raw=True) == []
+    assert torch.equal(model._view_index_of(torch.tensor([1, 0])), torch.tensor([1, 0], device="cuda"))     # a CPU tensor: as a list
+
+
+def test_view_ids_negative_select_what_index_select_does_and_out_of_range_give_nan():
+    """Valid negative ids (a list through the cached index, or a device tensor straight to the kernel) select what torch.index_select selects with
+    the ids made positive, bit for bit.  A device tensor with an id out of range cannot be checked on the host inside a captured step: its row is
+    NaN in every selected map, texel layout and warp map -- never what the buffer held before."""
+    from gens_amd import lib as L, ops
+    from gens_amd.ops.base import pack_maps
+    model = _finetune_model(False)
+    feats = list(model.features)
+    nv = feats[0].shape[0]
+    full = pack_maps(feats)
+    warp_full = ops.build_warp_features(feats[:3])[0] if len(feats) >= 3 else None
+
+    want_maps = feats + list(full) + ([warp_full] if warp_full is not None else [])
+    for ids in ([-1, 0, -nv], torch.tensor([-1, 1 - nv, 0], device="cuda")):
+        index = model._view_index_of(ids)
+        pos = torch.tensor([v % nv for v in (ids.tolist() if torch.is_tensor(ids) else ids)], device="cuda")
+        if not torch.is_tensor(ids):
+            assert torch.equal(index, pos)
+        got = model._select_frozen_views(index)
+        order = [g for g in got] + [g._gens_tex[2] for g in got] + ([got[0]._gens_warp[2][0]] if warp_full is not None else [])
+        assert len(order) == len(want_maps)
+        for a, m in zip(order, want_maps):
+            assert torch.equal(a, m.index_select(0, pos))
+    # out of range on the device: NaN rows, the valid rows as index_select's; stale memory made visible first (a sentinel in the freed blocks)
+    bad = torch.tensor([1, nv + 2, 0, -nv - 1], device="cuda")
+    sizes = [(4,) + tuple(m.shape[1:]) for m in want_maps]
+    junk = [torch.full(s, 7.0, device="cuda") for s in sizes]
+    del junk
+    L.profile_begin()
+    got = model._select_frozen_views(bad)
+    names = [name for name, _, _, _ in L.profile_end(raw=True)]
+    assert names.count("gens_select_views") == 1, names
+    order = [g for g in got] + [g._gens_tex[2] for g in got] + ([got[0]._gens_warp[2][0]] if warp_full is not None else [])
+    assert len(order) == len(want_maps)
+    for a, m in zip(order, want_maps):
+        assert torch.equal(a[[0, 2]], m.index_select(0, torch.tensor([1, 0], device="cuda")))
+        assert bool(torch.isnan(a[[1, 3]]).all())
+    # the kernel alone, into buffers holding a sentinel: every element of an out-of-range row is written
+    src = [m.contiguous() for m in want_maps]
+    dst = [torch.full((4,) + tuple(m.shape[1:]), 7.0, device="cuda") for m in src]
+    L.call("gens_select_views", L.ptr_table(src, align=16), L.ptr_table(dst, align=16), L.int_table([t[0].numel() for t in src]),
+           L.int_table([t.shape[0] for t in src]), len(src), L.ptr(bad, torch.long), 4, L.stream())
+    for a, m in zip(dst, src):
+        assert torch.equal(a[[0, 2]], m.index_select(0, torch.tensor([1, 0], device="cuda")))
+        assert bool(torch.isnan(a[[1, 3]]).all())
+
+
 def test_masks_that_arrive_with_their_bits_keep_them_through_a_captured_step():
     """The volume build hands out its masks with their bit-packed copies (ops.volume_build -> `_gens_bits`): the captured step holds no packing launch,
     every replay copies the step's words beside the step's masks -- or packs them when a step's masks come bare.  The masks CHANGE from step to step

@@ -557,6 +557,41 @@ def test_k2_second_order_outside_the_cube_vs_fd64_of_aten(ops):
     assert ((pts.abs() > 1).any(-1)).float().mean() > 0.5
 
 
+# the three K2 tests above once more with kernels.k2_bricks_min = 1: every volume gradient (first and second order) through the brick entries,
+# which their small point sets never reach at the default threshold
+def _through_the_bricks(ops, monkeypatch, run):
+    """-> the entry points `run` called with k2_bricks_min = 1."""
+    from gens_amd import lib as L
+    monkeypatch.setattr(ops.kernels, "k2_bricks_min", 1)
+    calls, real = [], L.call
+    monkeypatch.setattr(L, "call", lambda nm, *a, **k: (calls.append(nm), real(nm, *a, **k))[1])
+    try:
+        run()
+    finally:
+        monkeypatch.setattr(L, "call", real)
+    return calls
+
+
+def _bricks_only(calls):
+    assert "gens_lookup_volume_bwd_bricks" in calls and "gens_lookup_volume_bwd2_bricks" in calls, calls
+    assert "gens_lookup_volume_bwd" not in calls and "gens_lookup_volume_bwd2" not in calls, calls
+
+
+@pytest.mark.parametrize("packed", [False, True])
+def test_k2_lookup_golden_through_the_bricks(ops, golden, packed, monkeypatch):
+    calls = _through_the_bricks(ops, monkeypatch, lambda: test_k2_lookup_golden(ops, golden, packed))
+    if not packed:                                                   # (packed: no volume gradient is asked for, nothing to scatter)
+        _bricks_only(calls)
+
+
+def test_k2_second_order_with_volume_cotangent_vs_oracle_through_the_bricks(ops, monkeypatch):
+    _bricks_only(_through_the_bricks(ops, monkeypatch, lambda: test_k2_second_order_with_volume_cotangent_vs_oracle(ops)))
+
+
+def test_k2_second_order_outside_the_cube_vs_fd64_of_aten_through_the_bricks(ops, monkeypatch):
+    _bricks_only(_through_the_bricks(ops, monkeypatch, lambda: test_k2_second_order_outside_the_cube_vs_fd64_of_aten(ops)))
+
+
 def second_order_fd64_case():
     """-> (vols, pts, gO, ggG, gP2_fd, ggO_fd, gV2_fd), all float64 (see test_k2_second_order_outside_the_cube_vs_fd64_of_aten)."""
     import torch.nn.functional as F
