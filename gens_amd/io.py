@@ -41,12 +41,19 @@ def write_ply(path, vertices, triangles):
         f.write(faces.tobytes())
 
 
+_PLY_TYPES = {b"char": "i1", b"int8": "i1", b"uchar": "u1", b"uint8": "u1", b"short": "<i2", b"int16": "<i2", b"ushort": "<u2", b"uint16": "<u2",
+              b"int": "<i4", b"int32": "<i4", b"uint": "<u4", b"uint32": "<u4", b"float": "<f4", b"float32": "<f4", b"double": "<f8",
+              b"float64": "<f8"}
+
+
 def read_ply(path):
-    """Inverse of write_ply (binary little-endian, float x/y/z vertices, uchar-counted int triangles) -> (vertices, triangles)."""
+    """Inverse of write_ply (binary little-endian, x/y/z vertices, uchar-counted int triangles) -> (vertices, triangles).  Also reads what
+    the DTU scoring reads (evaluation/dtu_eval.py:84, 122): a file whose vertices carry further scalar properties (normals, colours), and a
+    point cloud without a face element, which gives triangles of shape (0, 3).  The vertices keep the file's x/y/z type."""
     with open(path, "rb") as f:
         if f.readline().strip() != b"ply":
             raise ValueError(f"{path}: not a PLY file")
-        nv = nf = None
+        nv, nf, element, props, face_props = None, 0, None, [], []
         while True:
             line = f.readline()
             if not line:
@@ -54,13 +61,30 @@ def read_ply(path):
             words = line.split()
             if words[:1] == [b"format"] and words[1] != b"binary_little_endian":
                 raise ValueError(f"{path}: only binary_little_endian is read")
-            if words[:2] == [b"element", b"vertex"]:
-                nv = int(words[2])
-            if words[:2] == [b"element", b"face"]:
-                nf = int(words[2])
+            if words[:1] == [b"element"]:
+                element = words[1]
+                if element == b"vertex":
+                    nv = int(words[2])
+                elif element == b"face":
+                    nf = int(words[2])
+                elif int(words[2]):
+                    raise ValueError(f"{path}: element {element.decode()} is not read")
+            if words[:1] == [b"property"]:
+                if element == b"vertex":
+                    if words[1] == b"list" or words[1] not in _PLY_TYPES:
+                        raise ValueError(f"{path}: vertex property {line.decode().strip()!r} is not read")
+                    props.append((words[2].decode(), _PLY_TYPES[words[1]]))
+                elif element == b"face":
+                    face_props.append(words[1:])
             if words[:1] == [b"end_header"]:
                 break
-        v = np.frombuffer(f.read(12 * nv), dtype="<f4").reshape(nv, 3)
+        if nv is None or not all(c in [p for p, _ in props] for c in "xyz"):
+            raise ValueError(f"{path}: no vertex element with x, y, z")
+        rows = np.frombuffer(f.read(np.dtype(props).itemsize * nv), dtype=props)
+        v = np.stack([rows["x"], rows["y"], rows["z"]], axis=-1) if nv else np.zeros((0, 3), dtype=props[0][1])
+        if nf and (len(face_props) != 1 or face_props[0][0] != b"list" or _PLY_TYPES.get(face_props[0][1]) != "u1" or
+                   _PLY_TYPES.get(face_props[0][2]) not in ("<i4", "<u4")):
+            raise ValueError(f"{path}: faces must be one uchar-counted list of int")
         faces = np.frombuffer(f.read(13 * nf), dtype=[("n", "u1"), ("idx", "<i4", (3,))])
         if nf and not (faces["n"] == 3).all():
             raise ValueError(f"{path}: non-triangular face")

@@ -20,6 +20,7 @@ _p = C.c_void_p
 _i = C.c_int
 _l = C.c_int64
 _f = C.c_float
+_d = C.c_double
 _pp = C.POINTER(C.c_void_p)
 _ip = C.POINTER(C.c_int)
 _fp = C.POINTER(C.c_float)
@@ -51,6 +52,11 @@ class CompositeGrad(C.Structure):
 class MeshGridArgs(C.Structure):       # gens_mesh_grid (K23)
     _fields_ = [(n, _p) for n in ("vertices", "triangles", "cell_start", "cell_faces")] + [("n_faces", _l)] + [
         (n, _f) for n in ("lo_x", "lo_y", "lo_z", "cell")] + [(n, _i) for n in ("nx", "ny", "nz")]
+
+
+class PointGridArgs(C.Structure):      # gens_point_grid (K24)
+    _fields_ = [(n, _p) for n in ("points", "sorted", "cell_start", "cell_points")] + [("n", _l)] + [
+        (n, _d) for n in ("lo_x", "lo_y", "lo_z", "cell")] + [(n, _i) for n in ("nx", "ny", "nz")]
 
 
 # name -> argtypes, mirroring include/gens_hip.h declaration by declaration
@@ -173,6 +179,12 @@ SIGNATURES = {
     "gens_view_rays_hit_faces": [C.POINTER(MeshGridArgs), _p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p],
     "gens_face_cc_hook": [_p, _l, _p, _l, _p],
     "gens_face_cc_compress": [_p, _l, _p, _p],
+    "gens_mesh_sample_count": [_p, _l, _p, _l, _d, _p, _p],
+    "gens_mesh_sample_emit": [_p, _l, _p, _l, _d, _p, _l, _p, _p],
+    "gens_point_grid_count": [C.POINTER(PointGridArgs), _p, _p],
+    "gens_point_grid_fill": [C.POINTER(PointGridArgs), _p, _p],
+    "gens_radius_downsample_round": [C.POINTER(PointGridArgs), _p, _d, _p, _p, _p, _p],
+    "gens_nearest_point": [C.POINTER(PointGridArgs), _p, _l, _d, _p, _p, _p],
 }
 
 _lib = None

@@ -16,6 +16,7 @@ is what it was when ops was one module:
     ops.conv3d    K15 / K16: the 3 x 3 x 3 convolutions and the instance norm + ReLU of the cost-volume U-Net.
     ops.blend     K7 (fused source-view look-up + BlendingNetwork in inference) and K18 (the same for a training step).
     ops.conv2d    K21: the depth-wise 2-D convolutions of the MnasNet trunk.
+    ops.points    K24: mesh sampling, radius down-sampling and capped nearest neighbours of the DTU scoring (evaluation/dtu_eval.py).
 """
 from .base import *  # noqa: F401,F403
 from .volume import *  # noqa: F401,F403
@@ -27,3 +28,4 @@ from .gemm import *  # noqa: F401,F403
 from .conv3d import *  # noqa: F401,F403
 from .blend import *  # noqa: F401,F403
 from .conv2d import *  # noqa: F401,F403
+from .points import *  # noqa: F401,F403

@@ -56,7 +56,8 @@ const char* gens_last_error(void);
  *       too), gens_select_views (the views of a fine-tune step out of the frozen maps and their layouts in one launch),
  *       gens_lookup_volume_bwd_bricks / _bwd2_bricks + gens_lookup_scatter_bricks_scratch_bytes (K2's volume-gradient scatter brick by brick).
  *       Later additions that change no existing entry keep 12: gens_sdf_{value,grad}_bf16x3 + gens_sdf_bf16x3_pieces, and K23's
- *       gens_mesh_grid_{count,fill}, gens_ray_first_hit, gens_view_rays_hit_faces, gens_face_cc_{hook,compress}. */
+ *       gens_mesh_grid_{count,fill}, gens_ray_first_hit, gens_view_rays_hit_faces, gens_face_cc_{hook,compress}, and K24's
+ *       gens_mesh_sample_{count,emit}, gens_point_grid_{count,fill}, gens_radius_downsample_round, gens_nearest_point. */
 int gens_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -703,6 +704,49 @@ int gens_view_rays_hit_faces(const gens_mesh_grid* grid, const float* masks, con
                              float inv_scale, uint8_t* flags, int32_t* any_miss, void* stream);
 int gens_face_cc_hook(const int32_t* pairs, int64_t n_pairs, int32_t* parent, int64_t n_faces, void* stream);
 int gens_face_cc_compress(const int32_t* parent, int64_t n_faces, int32_t* label, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * K24  the three hot steps of the DTU scoring (evaluation/dtu_eval.py), all geometry in float64 as the script computes it.  Every new
+ *      entry checks its arguments before any launch (null pointers, negative sizes, a radius / density / cap that is not positive:
+ *      GENS_EINVAL).  The ABI version stays 12: no existing entry changes.
+ *   gens_mesh_sample_count / _emit (dtu_eval.py:11-20, 61-78): vertices (n_vertices, 3) float64, triangles (n_triangles, 3) int32.
+ *     count: counts (n_triangles) int64 = the lattice points of every triangle ((i + 0.5) / n1 + (j + 0.5) / n2 < 1 with the script's
+ *     n1, n2; 0 for a triangle of zero area, with an index out of range, or with n1 or n2 = 0; 2^40 for a triangle with more than 2^20
+ *     lattice steps along an edge, which emit skips -- the caller's total shows it).  emit: offsets (n_triangles) int64 = the exclusive
+ *     scan of the counts, total = their sum (< 2^31); out (total, 3) float64, triangle by triangle, i major, j minor, each point
+ *     (v1 k0 + v2 k1) + p0 in the script's operations.
+ *   gens_point_grid (HOST struct, device pointers inside): nx * ny * nz (< 2^31) cubic cells of edge `cell` from (lo_x, lo_y, lo_z) over
+ *     points (n, 3) float64; a point outside the box counts for the nearest border cell.  cell_start (cells + 1) int32 = the exclusive scan
+ *     of gens_point_grid_count's counts (which ACCUMULATE); gens_point_grid_fill (cursor: (cells) int32 zero-filled scratch) writes
+ *     cell_points (n) int32 = the point ids cell by cell (any order inside a cell) and sorted (n, 3) = their coordinates in that order.
+ *     count / fill read `points`; the two entries below read `sorted`, `cell_start` and `cell_points`.
+ *   gens_radius_downsample_round (dtu_eval.py:94-102): one round of the sequential greedy's mask over the cell-ordered cloud.  rank (n)
+ *     int32 = the visiting position of the point in every slot; states (n) uint8, 0 undecided, 1 kept, 2 removed: state_out = state_in
+ *     with every undecided point decided whose earlier-visited neighbours within the radius (d^2 <= radius^2) are all decided --
+ *     removed if one of them is kept, else kept.  *undecided (int32) ACCUMULATES the points still undecided.  radius <= cell
+ *     (GENS_ELIMIT otherwise).  Starting from zeros, rounds until nothing is undecided give exactly the script's mask.
+ *   gens_nearest_point (:127-130, 140-142): for queries (n_queries, 3) float64 the distance to the nearest grid point and its id, the
+ *     smallest id among equal distances; +inf and -1 where nothing is closer than max_dist (+inf: no cap).
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    const double* points;
+    double* sorted;
+    const int32_t* cell_start;
+    int32_t* cell_points;
+    int64_t n;
+    double lo_x, lo_y, lo_z, cell;
+    int nx, ny, nz;
+} gens_point_grid;
+int gens_mesh_sample_count(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, double density,
+                           int64_t* counts, void* stream);
+int gens_mesh_sample_emit(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_triangles, double density,
+                          const int64_t* offsets, int64_t total, double* out, void* stream);
+int gens_point_grid_count(const gens_point_grid* grid, int32_t* counts, void* stream);
+int gens_point_grid_fill(const gens_point_grid* grid, int32_t* cursor, void* stream);
+int gens_radius_downsample_round(const gens_point_grid* grid, const int32_t* rank, double radius, const uint8_t* state_in, uint8_t* state_out,
+                                 int32_t* undecided, void* stream);
+int gens_nearest_point(const gens_point_grid* grid, const double* queries, int64_t n_queries, double max_dist, double* dist, int32_t* index,
+                       void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K14  C (m x n) = A^T B for tall row-major operands A (k x m), B (k x n), k >> m, n: the weight-gradient product of the training
