@@ -191,6 +191,18 @@ __device__ __forceinline__ float linspace_cpu(float start, float end, int steps,
     return i < steps / 2 ? fmaf(step, (float)i, start) : fmaf(-step, (float)(steps - 1 - i), end);
 }
 
+// The direction of the ray through pixel (x, y) of a view (cam: 21 floats, K^-1[:3,:3] row-major then c2w[:3,:4]), operation for operation
+// as torch evaluates clean_mesh.py:50-66 on the CPU (see view_rays_k).  Shared by K23's view_rays_k and K25's view_rays_counts_k.
+__device__ __forceinline__ void view_ray_dir(const float* __restrict__ cam, float x, float y, float rdir[3]) {
+    const float* K = cam;
+    const float* M = cam + 9;
+    float q[3], d[3];
+    for (int a = 0; a < 3; ++a) q[a] = ((0.0f + K[3 * a] * x) + K[3 * a + 1] * y) + K[3 * a + 2] * 1.0f;
+    const float nrm = (float)sqrt((double)fmaf(q[2], q[2], fmaf(q[1], q[1], q[0] * q[0])));
+    for (int a = 0; a < 3; ++a) d[a] = (float)((double)q[a] / (double)nrm);
+    for (int a = 0; a < 3; ++a) rdir[a] = ((0.0f + M[4 * a] * d[0]) + M[4 * a + 1] * d[1]) + M[4 * a + 2] * d[2];
+}
+
 // One thread per pixel of the upsampled image of view blockIdx.y.  cams: per view 21 floats, K^-1[:3,:3] row-major then c2w[:3,:4].
 // The ray is clean_mesh.py:50-66's, operation for operation as torch evaluates it on the CPU: (x, y, 1) from linspace; p = K^-1 p
 // (bmm: plain products, summed left to right from 0); p / ||p|| (the norm's sum of squares by fused multiply-adds, then a correctly
@@ -205,14 +217,9 @@ __global__ __launch_bounds__(256) void view_rays_k(gens_mesh_grid g, const float
     const int si = (int)fminf(floorf((float)i * inv_scale), (float)(h - 1));
     const int sj = (int)fminf(floorf((float)j * inv_scale), (float)(w - 1));
     if (!(masks[((int64_t)v * h + si) * w + sj] > 0.0f)) return;
-    const float* K = cams + 21 * v;
-    const float* M = K + 9;
-    const float x = linspace_cpu(0.0f, (float)(w - 1), wu, j), y = linspace_cpu(0.0f, (float)(h - 1), hu, i);
-    float q[3], d[3], rdir[3];
-    for (int a = 0; a < 3; ++a) q[a] = ((0.0f + K[3 * a] * x) + K[3 * a + 1] * y) + K[3 * a + 2] * 1.0f;
-    const float nrm = (float)sqrt((double)fmaf(q[2], q[2], fmaf(q[1], q[1], q[0] * q[0])));
-    for (int a = 0; a < 3; ++a) d[a] = (float)((double)q[a] / (double)nrm);
-    for (int a = 0; a < 3; ++a) rdir[a] = ((0.0f + M[4 * a] * d[0]) + M[4 * a + 1] * d[1]) + M[4 * a + 2] * d[2];
+    const float* M = cams + 21 * v + 9;
+    float rdir[3];
+    view_ray_dir(cams + 21 * v, linspace_cpu(0.0f, (float)(w - 1), wu, j), linspace_cpu(0.0f, (float)(h - 1), hu, i), rdir);
     WRay r;
     double t = INFINITY;
     int f = -1;
@@ -221,6 +228,34 @@ __global__ __launch_bounds__(256) void view_rays_k(gens_mesh_grid g, const float
         flags[f] = 1;       // (every writer stores the same value)
     else
         any_miss[0] = 1;
+}
+
+// K25 (evaluation/clean_meshes.py:212-246): the same walk for the full-resolution rays of the DTU finalising script.  One thread per pixel of
+// view blockIdx.y; a pixel casts iff its uint8 (dilated) mask value is > 128 (:235); the origin is advanced down the ray first,
+// rays_o + rays_d * dep_min (:239) as a float32 product and a float32 sum (the file is compiled unfused).  flags (nv, n_faces) and
+// any_miss (nv) are per view: the script's Counter sees a face, and the -1 of the misses, once per view.
+__global__ __launch_bounds__(256) void view_rays_counts_k(gens_mesh_grid g, const uint8_t* __restrict__ masks, const float* __restrict__ cams, int h,
+                                                          int w, float dep_min, uint8_t* __restrict__ flags, int32_t* __restrict__ any_miss) {
+    const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (pix >= (int64_t)h * w) return;
+    const int v = blockIdx.y;
+    if (!(masks[(int64_t)v * h * w + pix] > 128)) return;
+    const int i = (int)(pix / w), j = (int)(pix % w);
+    const float* M = cams + 21 * v + 9;
+    float rdir[3], o[3];
+    view_ray_dir(cams + 21 * v, linspace_cpu(0.0f, (float)(w - 1), w, j), linspace_cpu(0.0f, (float)(h - 1), h, i), rdir);
+    for (int a = 0; a < 3; ++a) {
+        const float adv = rdir[a] * dep_min;
+        o[a] = M[4 * a + 3] + adv;
+    }
+    WRay r;
+    double t = INFINITY;
+    int f = -1;
+    if (wray_setup(o[0], o[1], o[2], rdir[0], rdir[1], rdir[2], r)) f = first_hit(g, r, t);
+    if (f >= 0)
+        flags[(int64_t)v * g.n_faces + f] = 1;       // (every writer stores the same value)
+    else
+        any_miss[v] = 1;
 }
 
 // ------------------------------------------------------------------------------------------------ components
@@ -314,6 +349,18 @@ extern "C" int gens_view_rays_hit_faces(const gens_mesh_grid* g, const float* ma
     const dim3 grid(gens_blocks((int64_t)hu * wu, 256), (unsigned)nv);
     view_rays_k<<<grid, 256, 0, (hipStream_t)stream>>>(*g, masks, cams, h, w, hu, wu, inv_scale, flags, any_miss);
     return gens_launch_status("gens_view_rays_hit_faces");
+}
+
+extern "C" int gens_view_rays_hit_counts(const gens_mesh_grid* g, const uint8_t* masks, const float* cams, int nv, int h, int w, float dep_min,
+                                         uint8_t* flags, int32_t* any_miss, void* stream) {
+    if (int rc = check_grid(g, true, "gens_view_rays_hit_counts")) return rc;
+    GENS_CHECK_ARG(masks && cams && flags && any_miss, GENS_EINVAL, "gens_view_rays_hit_counts: null pointer");
+    GENS_CHECK_ARG(nv >= 1 && nv <= 65535 && h >= 1 && w >= 1 && (int64_t)h * w < ((int64_t)1 << 31), GENS_ELIMIT,
+                   "gens_view_rays_hit_counts: %d views of %dx%d", nv, h, w);
+    GENS_CHECK_ARG(isfinite(dep_min), GENS_ELIMIT, "gens_view_rays_hit_counts: dep_min = %g", (double)dep_min);
+    const dim3 grid(gens_blocks((int64_t)h * w, 256), (unsigned)nv);
+    view_rays_counts_k<<<grid, 256, 0, (hipStream_t)stream>>>(*g, masks, cams, h, w, dep_min, flags, any_miss);
+    return gens_launch_status("gens_view_rays_hit_counts");
 }
 
 extern "C" int gens_face_cc_hook(const int32_t* pairs, int64_t n_pairs, int32_t* parent, int64_t n_faces, void* stream) {

@@ -185,6 +185,9 @@ SIGNATURES = {
     "gens_point_grid_fill": [C.POINTER(PointGridArgs), _p, _p],
     "gens_radius_downsample_round": [C.POINTER(PointGridArgs), _p, _d, _p, _p, _p, _p],
     "gens_nearest_point": [C.POINTER(PointGridArgs), _p, _l, _d, _p, _p, _p],
+    "gens_dilate_u8": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _ip, _p],
+    "gens_vertex_mask_votes": [_p, _l, _p, _p, _i, _i, _i, _p, _p],
+    "gens_view_rays_hit_counts": [C.POINTER(MeshGridArgs), _p, _p, _i, _i, _i, _f, _p, _p, _p],
 }
 
 _lib = None

@@ -17,6 +17,7 @@ is what it was when ops was one module:
     ops.blend     K7 (fused source-view look-up + BlendingNetwork in inference) and K18 (the same for a training step).
     ops.conv2d    K21: the depth-wise 2-D convolutions of the MnasNet trunk.
     ops.points    K24: mesh sampling, radius down-sampling and capped nearest neighbours of the DTU scoring (evaluation/dtu_eval.py).
+    ops.finalize  K25: elliptical dilation, vertex mask votes and per-view ray hit counts of the DTU mesh finalising (evaluation/clean_meshes.py).
 """
 from .base import *  # noqa: F401,F403
 from .volume import *  # noqa: F401,F403
@@ -29,3 +30,4 @@ from .conv3d import *  # noqa: F401,F403
 from .blend import *  # noqa: F401,F403
 from .conv2d import *  # noqa: F401,F403
 from .points import *  # noqa: F401,F403
+from .finalize import *  # noqa: F401,F403

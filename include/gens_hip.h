@@ -57,7 +57,8 @@ const char* gens_last_error(void);
  *       gens_lookup_volume_bwd_bricks / _bwd2_bricks + gens_lookup_scatter_bricks_scratch_bytes (K2's volume-gradient scatter brick by brick).
  *       Later additions that change no existing entry keep 12: gens_sdf_{value,grad}_bf16x3 + gens_sdf_bf16x3_pieces, and K23's
  *       gens_mesh_grid_{count,fill}, gens_ray_first_hit, gens_view_rays_hit_faces, gens_face_cc_{hook,compress}, and K24's
- *       gens_mesh_sample_{count,emit}, gens_point_grid_{count,fill}, gens_radius_downsample_round, gens_nearest_point. */
+ *       gens_mesh_sample_{count,emit}, gens_point_grid_{count,fill}, gens_radius_downsample_round, gens_nearest_point, and K25's
+ *       gens_dilate_u8, gens_vertex_mask_votes, gens_view_rays_hit_counts. */
 int gens_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -747,6 +748,30 @@ int gens_radius_downsample_round(const gens_point_grid* grid, const int32_t* ran
                                  int32_t* undecided, void* stream);
 int gens_nearest_point(const gens_point_grid* grid, const double* queries, int64_t n_queries, double max_dist, double* dist, int32_t* index,
                        void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * K25  the device pieces of the DTU mesh finalising step (evaluation/clean_meshes.py).  Every entry checks its arguments before any launch.
+ *   gens_dilate_u8 (:124-127, :213-216): grey-scale dilation of interleaved uint8 images in (n, h, w, c), c = 1 or 3, into out
+ *     (n, h, w, channels), the first `channels` <= c channels of every pixel.  The structuring element has kh rows of kw columns (both odd,
+ *     at most 63), anchored at its centre; half_spans (kh) HOST ints: row i holds the columns kw / 2 - half_spans[i] .. kw / 2 +
+ *     half_spans[i] (negative: the row is empty).  Pixels outside the image do not take part (a border of 0).  Bit-equal to the maximum
+ *     over the element.
+ *   gens_vertex_mask_votes (:101-141): points (n_points, 3) float64; proj (nv, 3, 4) float32 (the first three rows of K4 @ E); masks
+ *     (nv, h, w) uint8, set where > 128.  votes (n_points) int32 = the number of views whose mask, framed by one pixel of ones, holds the
+ *     point's projection: q = P[:, :3] x + P[:, 3] in float64, q / q[2], rint, + 1, inside iff 0 <= u <= w, 0 <= v <= h and (u == 0 or
+ *     v == 0 or masks[v - 1][u - 1] > 128).  A projection that is not finite (q[2] == 0) counts as outside.
+ *   gens_view_rays_hit_counts (:212-246; the kernel lives beside K23's in k23_mesh_cull.hip): the rays of gen_rays_from_single_image for the
+ *     h x w pixels of nv views, generated in the kernel as gens_view_rays_hit_faces generates them; a pixel casts iff masks (nv, h, w)
+ *     uint8 is > 128 there; the origin is advanced to o + d * dep_min (a float32 product, then a float32 sum).  cams (nv, 21) as for
+ *     gens_view_rays_hit_faces.  flags (nv, n_faces) uint8 and any_miss (nv) int32 ACCUMULATE, per view: 1 for every face some ray of the
+ *     view hits first, 1 if some cast ray of the view misses.
+ * ---------------------------------------------------------------------------------------------------------- */
+int gens_dilate_u8(const uint8_t* in, uint8_t* out, int n, int h, int w, int c, int channels, int kw, int kh, const int* half_spans_host,
+                   void* stream);
+int gens_vertex_mask_votes(const double* points, int64_t n_points, const float* proj, const uint8_t* masks, int nv, int h, int w,
+                           int32_t* votes, void* stream);
+int gens_view_rays_hit_counts(const gens_mesh_grid* grid, const uint8_t* masks, const float* cams, int nv, int h, int w, float dep_min,
+                              uint8_t* flags, int32_t* any_miss, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K14  C (m x n) = A^T B for tall row-major operands A (k x m), B (k x n), k >> m, n: the weight-gradient product of the training
