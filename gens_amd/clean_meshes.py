@@ -34,6 +34,8 @@ import numpy as np
 import torch
 
 from .evaluation import DTU_TEST_SCANS
+from .io import device_of
+from .ops import kept_after_quirk  # noqa: F401  (:248-260, the `values[1:]` rule both cleaners share)
 
 VIEW_LISTS = ([23, 24, 33, 22, 15, 34, 14, 32, 16, 35, 25], [43, 33, 44, 42, 34, 32, 45, 23, 41, 24, 31])       # :322-325
 
@@ -55,10 +57,6 @@ def read_mask(filename):
         return np.ascontiguousarray(np.asarray(im.convert("RGB"))[:, :, 2])
 
 
-def _device(device=None):
-    return torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-
-
 def _channel0(masks, dev):
     m = torch.as_tensor(np.asarray(masks) if not isinstance(masks, torch.Tensor) else masks).to(dev)
     if m.dtype != torch.uint8 or m.dim() not in (3, 4):
@@ -71,7 +69,7 @@ def dilated_masks(masks, mask_dilated_size=11, device=None):
     the device (the script dilates all three channels and reads channel 0)."""
     from . import ops
     k = int(mask_dilated_size)
-    return ops.dilate_u8(_channel0(masks, _device(device)), ops.opencv_ellipse(k, k), k)
+    return ops.dilate_u8(_channel0(masks, device_of(device=device)), ops.opencv_ellipse(k, k), k)
 
 
 @torch.no_grad()
@@ -80,7 +78,7 @@ def clean_mesh_faces_by_mask(vertices, triangles, P, masks, minimal_vis=0, mask_
     the files -> (vertices, triangles) numpy: the vertices inside the dilated masks of more than `minimal_vis` views, the faces whose three
     vertices stay, re-indexed."""
     from . import ops
-    dev = _device(device)
+    dev = device_of(device=device)
     v_np, t_np = np.asarray(vertices), np.asarray(triangles).reshape(-1, 3)
     votes = ops.vertex_mask_votes(torch.as_tensor(v_np.astype(np.float64)).to(dev), torch.as_tensor(np.asarray(P, dtype=np.float32)).to(dev),
                                   dilated_masks(masks, mask_dilated_size, dev))
@@ -89,20 +87,6 @@ def clean_mesh_faces_by_mask(vertices, triangles, P, masks, minimal_vis=0, mask_
     index = torch.cumsum(keep, 0) - 1
     t = t[keep[t].all(dim=1)] if len(t) else t
     return v_np[keep.cpu().numpy()], index[t].cpu().numpy().astype(t_np.dtype)
-
-
-def kept_after_quirk(counts, any_miss, num_com_vis=2):
-    """:248-260 on device tensors: counts (F,) views that hit each face first, any_miss (nv,) -> (keep (F,) bool, len(values)).  values =
-    the sorted faces with counts >= num_com_vis, with -1 in front if at least num_com_vis views had a miss; values[1:] is kept."""
-    keep = counts >= num_com_vis
-    n_values = int(keep.sum())
-    if int((any_miss > 0).sum()) >= num_com_vis:
-        return keep, n_values + 1               # values[0] is the -1 of the misses
-    hit = torch.nonzero(keep).reshape(-1)
-    if len(hit):
-        keep = keep.clone()
-        keep[hit[0]] = False                    # values[1:] drops the smallest hit face instead
-    return keep, n_values
 
 
 @torch.no_grad()
@@ -114,9 +98,9 @@ def clean_mesh_faces_outside_frustum(vertices, triangles, P, masks, H=1200, W=16
     that receives n_faces and n_values, the two numbers of the script's "Surfaces/Kept" line.
     Deviations (both as io.clean_mesh_outside_frustum): an empty result where the reference raises because no component survives, and no
     merging of coincident vertices."""
-    from . import io, ops
+    from . import ops
     from .datasets.camera import load_K_Rt_from_P
-    dev = _device(device)
+    dev = device_of(device=device)
     v_np, t_np = np.asarray(vertices), np.asarray(triangles).reshape(-1, 3)
     m = dilated_masks(masks, mask_dilated_size, dev)
     if tuple(m.shape[1:]) != (int(H), int(W)):
@@ -130,11 +114,11 @@ def clean_mesh_faces_outside_frustum(vertices, triangles, P, masks, H=1200, W=16
     if len(t):
         grid = ops.build_mesh_grid(torch.as_tensor(v_np.astype(np.float64)).to(dev), t)
         counts, _, any_miss = ops.view_rays_hit_counts(grid, m, intrs, c2ws, dep_min)
-        keep, n_values = kept_after_quirk(counts, any_miss, num_com_vis)
+        keep, n_values = ops.kept_after_quirk(counts, any_miss, num_com_vis)
         t = t[keep]
     if stats is not None:
         stats.update(n_faces=len(t_np), n_values=n_values)
-    return io._large_components(v_np, t_np.dtype, t, min_faces)
+    return ops.large_components(v_np, t_np.dtype, t, min_faces)
 
 
 def finalize_dtu_meshes(root_dir, out_dir, n_view=3, set=0, scans=DTU_TEST_SCANS, device=None):  # noqa: A002 (the script's argument name)

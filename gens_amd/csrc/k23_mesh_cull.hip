@@ -8,7 +8,9 @@
 //            and Wald (JCGT 2013); both sides count (Embree's default), t > 0; the winner is the lexicographic minimum of (t, face), so
 //            the order inside a cell's list does not matter; the walk stops once the best t is <= the current cell's exit t;
 //   view rays: the same walk for the rays clean_mesh.py:50-66 builds, generated per pixel in the kernel (float32, in the order of ATen's CPU
-//            kernels), marking the faces hit and whether a masked ray missed;
+//            kernels), marking the faces hit and whether a masked ray missed -- one kernel template for this cleaner (float masks,
+//            upsampled, one row of flags for all views) and for K25's evaluation/clean_meshes.py:212-246 (uint8 masks, 1:1, rays that
+//            start dep_min down the ray, one row per view);
 //   components: union-find over the pairs of faces that share an edge used by exactly two faces (ECL-CC style: a hook launch with
 //            agent-scope atomics on every parent access, then a compress launch), roots = smallest face index of each component.
 //
@@ -192,7 +194,8 @@ __device__ __forceinline__ float linspace_cpu(float start, float end, int steps,
 }
 
 // The direction of the ray through pixel (x, y) of a view (cam: 21 floats, K^-1[:3,:3] row-major then c2w[:3,:4]), operation for operation
-// as torch evaluates clean_mesh.py:50-66 on the CPU (see view_rays_k).  Shared by K23's view_rays_k and K25's view_rays_counts_k.
+// as torch evaluates clean_mesh.py:50-66 on the CPU: p = K^-1 (x, y, 1) (bmm: plain products, summed left to right from 0); p / ||p|| (the
+// norm's sum of squares by fused multiply-adds, then a correctly rounded square root and quotient); R p the same way as K^-1 p.
 __device__ __forceinline__ void view_ray_dir(const float* __restrict__ cam, float x, float y, float rdir[3]) {
     const float* K = cam;
     const float* M = cam + 9;
@@ -203,47 +206,30 @@ __device__ __forceinline__ void view_ray_dir(const float* __restrict__ cam, floa
     for (int a = 0; a < 3; ++a) rdir[a] = ((0.0f + M[4 * a] * d[0]) + M[4 * a + 1] * d[1]) + M[4 * a + 2] * d[2];
 }
 
-// One thread per pixel of the upsampled image of view blockIdx.y.  cams: per view 21 floats, K^-1[:3,:3] row-major then c2w[:3,:4].
-// The ray is clean_mesh.py:50-66's, operation for operation as torch evaluates it on the CPU: (x, y, 1) from linspace; p = K^-1 p
-// (bmm: plain products, summed left to right from 0); p / ||p|| (the norm's sum of squares by fused multiply-adds, then a correctly
-// rounded square root and quotient); R p the same way as K^-1 p; origin c2w[:3, 3].  Active iff the nearest-upsampled mask > 0
-// (F.interpolate's rule: source = min(floor(dst * (float)(1 / upscale)), size - 1)).
-__global__ __launch_bounds__(256) void view_rays_k(gens_mesh_grid g, const float* __restrict__ masks, const float* __restrict__ cams, int h, int w,
-                                                   int hu, int wu, float inv_scale, uint8_t* __restrict__ flags, int32_t* __restrict__ any_miss) {
+// The view rays of both mesh cleaners: one thread per pixel of the (hu, wu) image of view blockIdx.y, (x, y) from linspace over the
+// (h, w) source image.  The pixel casts iff its nearest source pixel's mask is > threshold (F.interpolate's rule: source =
+// min(floor(dst * (float)(1 / upscale)), size - 1); the pixel itself for hu = h, wu = w, inv_scale = 1, as long as h and w are below 2^24,
+// where float32 still holds every index -- beyond any image: the entry points bound only h * w).  The ray is view_ray_dir's from
+// c2w[:3, 3] advanced down the ray, o + d * dep_min, as a float32 product and a float32 sum (the file is compiled unfused); for
+// dep_min = 0 a finite d adds +-0, which no later comparison sees, and a non-finite d is rejected by wray_setup either way.  View v marks
+// the faces its rays hit first in flags + v * flag_stride and a cast ray that missed in any_miss[v * miss_stride].
+//   K23 (utils/clean_mesh.py:45-78): float masks > 0, upsampled, dep_min = 0, one row for all views (strides 0, 0);
+//   K25 (evaluation/clean_meshes.py:212-246): uint8 (dilated) masks > 128 (:235), 1:1, dep_min (:239), one row per view (strides
+//   n_faces, 1): the script's Counter sees a face, and the -1 of the misses, once per view.
+template <typename MaskT>
+__global__ __launch_bounds__(256) void view_rays_k(gens_mesh_grid g, const MaskT* __restrict__ masks, MaskT threshold, const float* __restrict__ cams,
+                                                   int h, int w, int hu, int wu, float inv_scale, float dep_min, int64_t flag_stride,
+                                                   int miss_stride, uint8_t* __restrict__ flags, int32_t* __restrict__ any_miss) {
     const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (pix >= (int64_t)hu * wu) return;
     const int v = blockIdx.y;
     const int i = (int)(pix / wu), j = (int)(pix % wu);
     const int si = (int)fminf(floorf((float)i * inv_scale), (float)(h - 1));
     const int sj = (int)fminf(floorf((float)j * inv_scale), (float)(w - 1));
-    if (!(masks[((int64_t)v * h + si) * w + sj] > 0.0f)) return;
-    const float* M = cams + 21 * v + 9;
-    float rdir[3];
-    view_ray_dir(cams + 21 * v, linspace_cpu(0.0f, (float)(w - 1), wu, j), linspace_cpu(0.0f, (float)(h - 1), hu, i), rdir);
-    WRay r;
-    double t = INFINITY;
-    int f = -1;
-    if (wray_setup(M[3], M[7], M[11], rdir[0], rdir[1], rdir[2], r)) f = first_hit(g, r, t);
-    if (f >= 0)
-        flags[f] = 1;       // (every writer stores the same value)
-    else
-        any_miss[0] = 1;
-}
-
-// K25 (evaluation/clean_meshes.py:212-246): the same walk for the full-resolution rays of the DTU finalising script.  One thread per pixel of
-// view blockIdx.y; a pixel casts iff its uint8 (dilated) mask value is > 128 (:235); the origin is advanced down the ray first,
-// rays_o + rays_d * dep_min (:239) as a float32 product and a float32 sum (the file is compiled unfused).  flags (nv, n_faces) and
-// any_miss (nv) are per view: the script's Counter sees a face, and the -1 of the misses, once per view.
-__global__ __launch_bounds__(256) void view_rays_counts_k(gens_mesh_grid g, const uint8_t* __restrict__ masks, const float* __restrict__ cams, int h,
-                                                          int w, float dep_min, uint8_t* __restrict__ flags, int32_t* __restrict__ any_miss) {
-    const int64_t pix = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (pix >= (int64_t)h * w) return;
-    const int v = blockIdx.y;
-    if (!(masks[(int64_t)v * h * w + pix] > 128)) return;
-    const int i = (int)(pix / w), j = (int)(pix % w);
+    if (!(masks[((int64_t)v * h + si) * w + sj] > threshold)) return;
     const float* M = cams + 21 * v + 9;
     float rdir[3], o[3];
-    view_ray_dir(cams + 21 * v, linspace_cpu(0.0f, (float)(w - 1), w, j), linspace_cpu(0.0f, (float)(h - 1), h, i), rdir);
+    view_ray_dir(cams + 21 * v, linspace_cpu(0.0f, (float)(w - 1), wu, j), linspace_cpu(0.0f, (float)(h - 1), hu, i), rdir);
     for (int a = 0; a < 3; ++a) {
         const float adv = rdir[a] * dep_min;
         o[a] = M[4 * a + 3] + adv;
@@ -253,9 +239,9 @@ __global__ __launch_bounds__(256) void view_rays_counts_k(gens_mesh_grid g, cons
     int f = -1;
     if (wray_setup(o[0], o[1], o[2], rdir[0], rdir[1], rdir[2], r)) f = first_hit(g, r, t);
     if (f >= 0)
-        flags[(int64_t)v * g.n_faces + f] = 1;       // (every writer stores the same value)
+        flags[(int64_t)v * flag_stride + f] = 1;       // (every writer stores the same value)
     else
-        any_miss[v] = 1;
+        any_miss[v * miss_stride] = 1;
 }
 
 // ------------------------------------------------------------------------------------------------ components
@@ -338,28 +324,35 @@ extern "C" int gens_ray_first_hit(const gens_mesh_grid* g, const float* rays_o, 
     return gens_launch_status("gens_ray_first_hit");
 }
 
+// what the two view-ray entry points check alike: the grid with its lists, and the pointers
+static int check_view_rays(const gens_mesh_grid* g, const void* masks, const float* cams, const uint8_t* flags, const int32_t* any_miss,
+                           const char* who) {
+    if (int rc = check_grid(g, true, who)) return rc;
+    GENS_CHECK_ARG(masks && cams && flags && any_miss, GENS_EINVAL, "%s: null pointer", who);
+    return 0;
+}
+
 extern "C" int gens_view_rays_hit_faces(const gens_mesh_grid* g, const float* masks, const float* cams, int nv, int h, int w, int hu, int wu,
                                         float inv_scale, uint8_t* flags, int32_t* any_miss, void* stream) {
-    if (int rc = check_grid(g, true, "gens_view_rays_hit_faces")) return rc;
-    GENS_CHECK_ARG(masks && cams && flags && any_miss, GENS_EINVAL, "gens_view_rays_hit_faces: null pointer");
+    if (int rc = check_view_rays(g, masks, cams, flags, any_miss, "gens_view_rays_hit_faces")) return rc;
     GENS_CHECK_ARG(nv >= 1 && nv <= 65535 && h >= 1 && w >= 1 && hu >= 1 && wu >= 1 && (int64_t)hu * wu < ((int64_t)1 << 31) &&
                        (int64_t)h * w < ((int64_t)1 << 31),
                    GENS_ELIMIT, "gens_view_rays_hit_faces: %d views of %dx%d, upsampled %dx%d", nv, h, w, hu, wu);
     GENS_CHECK_ARG(inv_scale > 0.0f && isfinite(inv_scale), GENS_ELIMIT, "gens_view_rays_hit_faces: 1 / upscale = %g", (double)inv_scale);
     const dim3 grid(gens_blocks((int64_t)hu * wu, 256), (unsigned)nv);
-    view_rays_k<<<grid, 256, 0, (hipStream_t)stream>>>(*g, masks, cams, h, w, hu, wu, inv_scale, flags, any_miss);
+    view_rays_k<float><<<grid, 256, 0, (hipStream_t)stream>>>(*g, masks, 0.0f, cams, h, w, hu, wu, inv_scale, 0.0f, 0, 0, flags, any_miss);
     return gens_launch_status("gens_view_rays_hit_faces");
 }
 
 extern "C" int gens_view_rays_hit_counts(const gens_mesh_grid* g, const uint8_t* masks, const float* cams, int nv, int h, int w, float dep_min,
                                          uint8_t* flags, int32_t* any_miss, void* stream) {
-    if (int rc = check_grid(g, true, "gens_view_rays_hit_counts")) return rc;
-    GENS_CHECK_ARG(masks && cams && flags && any_miss, GENS_EINVAL, "gens_view_rays_hit_counts: null pointer");
+    if (int rc = check_view_rays(g, masks, cams, flags, any_miss, "gens_view_rays_hit_counts")) return rc;
     GENS_CHECK_ARG(nv >= 1 && nv <= 65535 && h >= 1 && w >= 1 && (int64_t)h * w < ((int64_t)1 << 31), GENS_ELIMIT,
                    "gens_view_rays_hit_counts: %d views of %dx%d", nv, h, w);
     GENS_CHECK_ARG(isfinite(dep_min), GENS_ELIMIT, "gens_view_rays_hit_counts: dep_min = %g", (double)dep_min);
     const dim3 grid(gens_blocks((int64_t)h * w, 256), (unsigned)nv);
-    view_rays_counts_k<<<grid, 256, 0, (hipStream_t)stream>>>(*g, masks, cams, h, w, dep_min, flags, any_miss);
+    view_rays_k<uint8_t><<<grid, 256, 0, (hipStream_t)stream>>>(*g, masks, (uint8_t)128, cams, h, w, h, w, 1.0f, dep_min, g->n_faces, 1, flags,
+                                                                 any_miss);
     return gens_launch_status("gens_view_rays_hit_counts");
 }
 

@@ -16,13 +16,6 @@ import torch
 DTU_TEST_SCANS = (24, 37, 40, 55, 63, 65, 69, 83, 97, 105, 106, 110, 114, 118, 122)
 
 
-def _device_of(*xs):
-    for x in xs:
-        if isinstance(x, torch.Tensor) and x.is_cuda:
-            return x.device
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def _f64_dev(x, dev):
     if isinstance(x, torch.Tensor):
         return x.detach().to(device=dev, dtype=torch.float64)
@@ -50,11 +43,11 @@ def dtu_chamfer(vertices, triangles, stl_points, obs_mask, bb, res, plane, *, po
       * distances at or beyond max_dist are dropped from the means, and the mean of an empty selection is NaN (:130, 142).
     All geometry is float64, as in the script."""
     from . import ops
-    dev = _device_of(vertices, triangles, stl_points, points)
+    from .io import as_numpy, device_of
+    dev = device_of(vertices, triangles, stl_points, points)
     if points is None:
         v = _f64_dev(vertices, dev).reshape(-1, 3)
-        t = torch.as_tensor(np.asarray(triangles.detach().cpu() if isinstance(triangles, torch.Tensor) else triangles).astype(np.int64),
-                            device=dev).reshape(-1, 3)
+        t = torch.as_tensor(as_numpy(triangles).astype(np.int64), device=dev).reshape(-1, 3)
         data_pcd = ops.sample_mesh_points(v, t, density)
     else:
         data_pcd = _f64_dev(points, dev).reshape(-1, 3)
@@ -70,7 +63,7 @@ def dtu_chamfer(vertices, triangles, stl_points, obs_mask, bb, res, plane, *, po
     inbound = ((data_down >= lo) & (data_down < hi)).sum(dim=-1) == 3            # :111
     data_in = data_down[inbound]
     res = torch.as_tensor(np.asarray(res, dtype=np.float64).reshape(-1)[:1], device=dev)
-    mask = torch.as_tensor(np.asarray(obs_mask.detach().cpu() if isinstance(obs_mask, torch.Tensor) else obs_mask) != 0, device=dev)
+    mask = torch.as_tensor(as_numpy(obs_mask) != 0, device=dev)
     data_grid = torch.round((data_in - torch.as_tensor(bb32[:1].astype(np.float64), device=dev)) / res).to(torch.int64)      # :114
     shape = torch.tensor(list(mask.shape), device=dev)
     grid_inbound = ((data_grid >= 0) & (data_grid < shape)).sum(dim=-1) == 3     # :115
@@ -82,7 +75,7 @@ def dtu_chamfer(vertices, triangles, stl_points, obs_mask, bb, res, plane, *, po
     dist_d2s, _ = ops.nearest_distance(data_in_obs, stl, max_dist)               # :127-128
     mean_d2s = dist_d2s[dist_d2s < max_dist].mean()                              # :130
 
-    p = torch.as_tensor(np.asarray(plane.detach().cpu() if isinstance(plane, torch.Tensor) else plane, dtype=np.float64).reshape(4), device=dev)
+    p = torch.as_tensor(as_numpy(plane).astype(np.float64).reshape(4), device=dev)
     above = (((p[0] * stl[:, 0] + p[1] * stl[:, 1]) + p[2] * stl[:, 2]) + p[3]) > 0      # :136-137 (numpy sums the four products left to right)
     stl_above = stl[above]
     dist_s2d, _ = ops.nearest_distance(stl_above, data_in, max_dist)             # :140-141
@@ -110,7 +103,7 @@ def evaluate_dtu(out_dir, dataset_dir, scans=DTU_TEST_SCANS, mode="mesh", densit
     from . import io
     if mode not in ("mesh", "pcd"):
         raise ValueError(f"evaluate_dtu: mode {mode!r} (mesh or pcd)")
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    dev = io.device_of(device=device)
     results = {}
     for scan in scans:
         if mode == "mesh":

@@ -138,11 +138,14 @@ def drop_small_components(vertices, triangles, min_faces=500):
     return v[used], remap[tri].astype(np.asarray(triangles).dtype if len(tri) else np.int64)
 
 
-def _as_numpy(x):
+def as_numpy(x):
     return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
 
 
-def _device_of(*xs):
+def device_of(*xs, device=None):
+    """`device` if given, else the device of the first HIP tensor among xs, else the current one."""
+    if device is not None:
+        return torch.device(device)
     for x in xs:
         if isinstance(x, torch.Tensor) and x.is_cuda:
             return x.device
@@ -164,36 +167,15 @@ def clean_mesh_outside_frustum(vertices, triangles, masks, intrs, c2ws, upscale=
     mesh; K12 emits one vertex per lattice edge, so vertices coincide only where a lattice value equals the threshold exactly, and no
     merge is done here."""
     from . import ops
-    v_np, t_np = _as_numpy(vertices), _as_numpy(triangles)
-    dev = _device_of(vertices, triangles, masks)
+    v_np, t_np = as_numpy(vertices), as_numpy(triangles)
+    dev = device_of(vertices, triangles, masks)
     v = torch.as_tensor(v_np, dtype=torch.float64).reshape(-1, 3).to(dev)
     t = torch.as_tensor(t_np.astype(np.int64)).reshape(-1, 3).to(dev)
     if len(t):
         grid = ops.build_mesh_grid(v, t)
-        flags, any_miss = ops.visible_faces(grid, masks, intrs, c2ws, upscale)
-        seen = flags.bool()
-        if not bool(any_miss.item()):                   # values[1:] drops the smallest hit face instead of the -1 of the misses
-            hit = torch.nonzero(seen).reshape(-1)
-            if len(hit):
-                seen[hit[0]] = False
-        t = t[seen]
-    return _large_components(v_np, t_np.dtype, t, min_faces)
-
-
-def _large_components(v_np, t_dtype, t, min_faces):
-    """The tail of clean_mesh_outside_frustum (clean_mesh.py:101-106) on device triangles t (F,3) int64."""
-    from . import ops
-    dev, n_v = t.device, len(v_np)
-    if len(t):
-        pairs = ops.face_adjacency(t, n_v)
-        label = ops.face_components(t, n_v, pairs).long()
-        in_graph = torch.zeros(len(t), device=dev, dtype=torch.bool)
-        in_graph[pairs.reshape(-1).long()] = True
-        t = t[in_graph & (torch.bincount(label, minlength=len(t))[label] >= min_faces)]
-    used = torch.zeros(n_v, device=dev, dtype=torch.bool)
-    used[t.reshape(-1)] = True
-    remap = torch.cumsum(used, 0) - 1
-    return v_np.reshape(-1, 3)[used.cpu().numpy()], remap[t].cpu().numpy().astype(t_dtype)
+        flags, any_miss = ops.visible_faces(grid, masks, intrs, c2ws, upscale)       # the union over the views: one view's counts
+        t = t[ops.kept_after_quirk(flags, any_miss, 1)[0]]
+    return ops.large_components(v_np, t_np.dtype, t, min_faces)
 
 
 @torch.no_grad()
@@ -201,9 +183,10 @@ def _drop_small_components_device(vertices, triangles, min_faces=500):
     """clean_mesh.py:101-106 on the device (K23), trimesh's rule: faces are joined across edges of exactly two faces, and a face without
     such a neighbour is in no component -> (vertices, triangles) numpy, unreferenced vertices removed in their order.  Equal to
     `drop_small_components` on manifold meshes (for min_faces >= 2)."""
-    v_np, t_np = _as_numpy(vertices), _as_numpy(triangles)
-    dev = _device_of(vertices, triangles)
-    return _large_components(v_np, t_np.dtype, torch.as_tensor(t_np.astype(np.int64)).reshape(-1, 3).to(dev), min_faces)
+    from . import ops
+    v_np, t_np = as_numpy(vertices), as_numpy(triangles)
+    dev = device_of(vertices, triangles)
+    return ops.large_components(v_np, t_np.dtype, torch.as_tensor(t_np.astype(np.int64)).reshape(-1, 3).to(dev), min_faces)
 
 
 @torch.no_grad()
@@ -215,8 +198,8 @@ def clean_mesh(vertices, triangles, masks, intrs, c2ws, dilation_radius=11, min_
     masks = masks.detach().cpu()
     if masks.dim() > 3:
         masks = masks.mean(dim=-1)
-    v_np = _as_numpy(vertices)
-    kept = clean_mesh_by_mask(v_np, _as_numpy(triangles), dilate_masks(masks, dilation_radius), intrs, c2ws, min_nb_visible)
+    v_np = as_numpy(vertices)
+    kept = clean_mesh_by_mask(v_np, as_numpy(triangles), dilate_masks(masks, dilation_radius), intrs, c2ws, min_nb_visible)
     return clean_mesh_outside_frustum(v_np, kept, masks, intrs, c2ws, upscale=upscale, min_faces=min_faces)
 
 

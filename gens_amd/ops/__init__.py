@@ -10,14 +10,14 @@ is what it was when ops was one module:
     ops.volume    K1: Volume.agg_mean_var (volume.py:13-63), forward and backward, one level or a scene's pyramid.
     ops.lookup    K2 / K2'' (lookup_volume with first and second derivatives), K3 (nearest masks, ray points), K4 (lookup_feature).
     ops.rays      K5-K7 (hierarchical sampling), K8 (compositing and the step-boundary kernels around it), K9 (patch reads, surface patch warp), K10 (TV).
-    ops.geometry  K11 (lattice points) and K12 (iso-surface extraction on the device).
+    ops.geometry  K11 (lattice points), K12 (iso-surface extraction on the device), K23 / K25's view rays, face components and culling tail.
     ops.sdf       K6 (the fused SDF network in inference) and K17 (the SDF network of a training step).
     ops.gemm      K14: a^T b for tall operands, the weight-gradient product of the training step.
     ops.conv3d    K15 / K16: the 3 x 3 x 3 convolutions and the instance norm + ReLU of the cost-volume U-Net.
     ops.blend     K7 (fused source-view look-up + BlendingNetwork in inference) and K18 (the same for a training step).
     ops.conv2d    K21: the depth-wise 2-D convolutions of the MnasNet trunk.
     ops.points    K24: mesh sampling, radius down-sampling and capped nearest neighbours of the DTU scoring (evaluation/dtu_eval.py).
-    ops.finalize  K25: elliptical dilation, vertex mask votes and per-view ray hit counts of the DTU mesh finalising (evaluation/clean_meshes.py).
+    ops.finalize  K25: elliptical dilation and vertex mask votes of the DTU mesh finalising (evaluation/clean_meshes.py).
 """
 from .base import *  # noqa: F401,F403
 from .volume import *  # noqa: F401,F403

@@ -1,5 +1,5 @@
-"""K25: the device pieces of the DTU mesh finalising step (evaluation/clean_meshes.py): OpenCV's elliptical dilation, the per-vertex mask
-votes and the per-view first-hit flags of the full-resolution rays.
+"""K25: the device pieces of the DTU mesh finalising step (evaluation/clean_meshes.py) that are its own: OpenCV's elliptical dilation and
+the per-vertex mask votes.  Its ray step (view_rays_hit_counts) is in ops/geometry.py, beside K23's.
 
 Part of gens_amd.ops (see ops/__init__.py); citations are relative to /root/reference."""
 from .base import *  # noqa: F401,F403
@@ -67,36 +67,6 @@ def vertex_mask_votes(points, proj, masks):
     L.call("gens_vertex_mask_votes", L.ptr(p, torch.float64), p.shape[0], L.ptr(pr), L.ptr(m, torch.uint8), nv, h, w, L.ptr(votes, torch.int32),
            L.stream(), nbytes=p.shape[0] * 28)
     return votes
-
-
-def finalize_ray_cams(intrs, c2ws):
-    """(nv,4,4) intrinsics and camera-to-world -> (nv,21) float32 on the host: the inverse of each float32 3x3 K on the CPU (as
-    clean_meshes.py:51 takes it from the [:3,:3] block it is handed at :223) and c2w[:3,:4]."""
-    intrs, c2ws = torch.as_tensor(intrs).detach().cpu(), torch.as_tensor(c2ws).detach().cpu().float()
-    return torch.stack([torch.cat([torch.inverse(intrs[i][:3, :3].float()).reshape(-1), c2ws[i][:3, :4].reshape(-1)]) for i in range(intrs.shape[0])])
-
-
-def view_rays_hit_counts(grid, masks, intrs, c2ws, dep_min=425):
-    """The ray loop of clean_mesh_faces_outside_frustum (clean_meshes.py:212-246) in one launch: every pixel of every view whose uint8
-    mask is > 128 casts gen_rays_from_single_image's ray from o + d * dep_min.  masks (nv,H,W) uint8, intrs / c2ws (nv,4,4) ->
-    (counts (F,) int32: the number of views in which some ray hits the face first; flags (nv,F) uint8: per view; any_miss (nv,) int32: 1
-    where a cast ray of the view missed)."""
-    dev = grid.vertices.device
-    m = _c(masks.detach().to(dev))
-    if m.dtype != torch.uint8 or m.dim() != 3:
-        raise ValueError("view_rays_hit_counts: (nv,H,W) uint8 masks")
-    nv, h, w = m.shape
-    cams = finalize_ray_cams(intrs, c2ws).to(dev)
-    nf = grid.n_faces
-    flags = torch.zeros(nv, max(nf, 1), device=dev, dtype=torch.uint8)
-    any_miss = torch.zeros(nv, device=dev, dtype=torch.int32)
-    if nf:
-        L.call("gens_view_rays_hit_counts", C.byref(grid.args()), L.ptr(m, torch.uint8), L.ptr(cams), nv, h, w, float(dep_min),
-               L.ptr(flags, torch.uint8), L.ptr(any_miss, torch.int32), L.stream())
-    else:
-        any_miss += (m > 128).reshape(nv, -1).any(1).to(torch.int32)       # (an empty mesh: every cast ray misses)
-        flags = flags[:, :0]
-    return flags.sum(0, dtype=torch.int32), flags, any_miss
 
 
 __all__ = [n_ for n_ in dir() if not n_.startswith("__")]

@@ -1,4 +1,5 @@
-"""K11 (lattice points), K12 (iso-surface extraction on the device) and K23 (ray casting against the extracted mesh, face components).
+"""K11 (lattice points), K12 (iso-surface extraction on the device) and K23 / K25's mesh culling (ray casting against the extracted mesh,
+the view rays of both cleaning scripts, face components and the culling tail the two share).
 
 Part of gens_amd.ops (see ops/__init__.py); citations are relative to /root/reference."""
 from .base import *  # noqa: F401,F403
@@ -55,7 +56,7 @@ def marching_cubes(u, threshold=0.0):
 
 # ------------------------------------------------------------------------------------------------------------------
 # K23  first hits against a triangle mesh and its face components (utils/clean_mesh.py:38-106: pyembree's intersects_first, trimesh's
-#      face_adjacency + connected_components)
+#      face_adjacency + connected_components); the same kernels under K25's ray step (evaluation/clean_meshes.py:212-281)
 # ------------------------------------------------------------------------------------------------------------------
 class MeshGrid:
     """A triangle mesh on the device with the uniform grid of K23 over it: about two cubic cells per face (at most 512 per axis), every
@@ -143,28 +144,62 @@ def ray_mesh_first_hit(rays_o, rays_d, grid):
     return face, t
 
 
-def view_ray_cams(intrs, c2ws):
-    """(nv,4,4) intrinsics and camera-to-world -> (nv,21) float32 on the host: K^-1[:3,:3] (torch.inverse of each float32 4x4 on the CPU, as
-    clean_mesh.py:60 takes it) and c2w[:3,:4]."""
-    intrs, c2ws = intrs.detach().cpu().float(), c2ws.detach().cpu().float()
-    return torch.stack([torch.cat([intrs[i].inverse()[:3, :3].reshape(-1), c2ws[i][:3, :4].reshape(-1)]) for i in range(intrs.shape[0])])
+def view_ray_cams(intrs, c2ws, invert="4x4"):
+    """(nv,4,4) intrinsics and camera-to-world -> (nv,21) float32 on the host: K^-1[:3,:3] and c2w[:3,:4].  K^-1 is torch.inverse on the
+    CPU of each float32 4x4 (invert="4x4", as clean_mesh.py:60 takes it) or of its 3x3 block (invert="3x3", as clean_meshes.py:51 takes it
+    from the [:3,:3] it is handed at :223); the two differ in the last bits, and each script's rays need its own."""
+    if invert not in ("4x4", "3x3"):
+        raise ValueError(f"view_ray_cams: invert={invert!r} (4x4 or 3x3)")
+    intrs, c2ws = torch.as_tensor(intrs).detach().cpu(), torch.as_tensor(c2ws).detach().cpu().float()
+    def kinv(k):
+        # each matrix goes to float32 where its script converts it, the 3x3 block once it is cut out: the last bits of torch.inverse
+        # depend on the memory layout it is handed, and the block of a float64 input reaches it as a contiguous copy
+        if invert == "4x4":
+            return k.float().inverse()[:3, :3]
+        return torch.inverse(k[:3, :3].float())
+
+    return torch.stack([torch.cat([kinv(intrs[i]).reshape(-1), c2ws[i][:3, :4].reshape(-1)]) for i in range(intrs.shape[0])])
+
+
+def _cast_view_rays(entry, grid, masks, intrs, c2ws, *shape, invert, rows):
+    """The launch both view-ray operators share: the camera table, zeroed flags (rows, F) and any_miss (rows,), and `entry` on masks
+    (nv,H,W) with `shape` = its arguments between (nv, H, W) and the outputs -> (flags, any_miss)."""
+    dev = grid.vertices.device
+    nv, h, w = masks.shape
+    cams = view_ray_cams(intrs, c2ws, invert).to(dev)
+    flags = torch.zeros(rows, max(grid.n_faces, 1), device=dev, dtype=torch.uint8)
+    any_miss = torch.zeros(rows, device=dev, dtype=torch.int32)
+    L.call(entry, C.byref(grid.args()), L.ptr(masks, masks.dtype), L.ptr(cams), nv, h, w, *shape, L.ptr(flags, torch.uint8),
+           L.ptr(any_miss, torch.int32), L.stream())
+    return flags[:, :grid.n_faces], any_miss
 
 
 def visible_faces(grid, masks, intrs, c2ws, upscale):
     """The first-hit half of clean_mesh_outside_frustum (clean_mesh.py:45-78) in one launch: every pixel of every view upsampled by
     `upscale` whose nearest-upsampled mask is > 0 casts the ray clean_mesh.py:50-66 builds.  masks (nv,H,W) (the raw, view-averaged masks),
     intrs / c2ws (nv,4,4) -> (flags (F,) uint8: 1 for every face some ray hits first, any_miss (1,) int32: 1 if some cast ray missed)."""
-    dev = grid.vertices.device
-    m = _c(masks.detach().to(device=dev, dtype=_f32))
-    nv, h, w = m.shape
-    cams = view_ray_cams(intrs, c2ws).to(dev)
-    hu, wu = int(h * upscale), int(w * upscale)
+    m = _c(masks.detach().to(device=grid.vertices.device, dtype=_f32))
+    _, h, w = m.shape
     inv_scale = float(torch.tensor(1.0 / upscale, dtype=torch.float32))
-    flags = torch.zeros(max(grid.n_faces, 1), device=dev, dtype=torch.uint8)
-    any_miss = torch.zeros(1, device=dev, dtype=torch.int32)
-    L.call("gens_view_rays_hit_faces", C.byref(grid.args()), L.ptr(m), L.ptr(cams), nv, h, w, hu, wu, inv_scale, L.ptr(flags, torch.uint8),
-           L.ptr(any_miss, torch.int32), L.stream())
-    return flags[:grid.n_faces], any_miss
+    flags, any_miss = _cast_view_rays("gens_view_rays_hit_faces", grid, m, intrs, c2ws, int(h * upscale), int(w * upscale), inv_scale,
+                                      invert="4x4", rows=1)
+    return flags[0], any_miss
+
+
+def view_rays_hit_counts(grid, masks, intrs, c2ws, dep_min=425):
+    """The ray loop of clean_mesh_faces_outside_frustum (clean_meshes.py:212-246) in one launch: every pixel of every view whose uint8
+    mask is > 128 casts gen_rays_from_single_image's ray from o + d * dep_min.  masks (nv,H,W) uint8, intrs / c2ws (nv,4,4) ->
+    (counts (F,) int32: the number of views in which some ray hits the face first; flags (nv,F) uint8: per view; any_miss (nv,) int32: 1
+    where a cast ray of the view missed)."""
+    m = _c(masks.detach().to(grid.vertices.device))
+    if m.dtype != torch.uint8 or m.dim() != 3:
+        raise ValueError("view_rays_hit_counts: (nv,H,W) uint8 masks")
+    if grid.n_faces:
+        flags, any_miss = _cast_view_rays("gens_view_rays_hit_counts", grid, m, intrs, c2ws, float(dep_min), invert="3x3", rows=m.shape[0])
+    else:                                       # (an empty mesh has no arrays to hand the kernel: every cast ray misses)
+        flags = torch.zeros(m.shape[0], 0, device=m.device, dtype=torch.uint8)
+        any_miss = (m > 128).reshape(m.shape[0], -1).any(1).to(torch.int32)
+    return flags.sum(0, dtype=torch.int32), flags, any_miss
 
 
 def face_adjacency(triangles, n_vertices):
@@ -203,6 +238,38 @@ def face_components(triangles, n_vertices, pairs=None):
         L.call("gens_face_cc_hook", L.ptr(pairs, i32), pairs.shape[0], L.ptr(parent, i32), nf, L.stream())
     L.call("gens_face_cc_compress", L.ptr(parent, i32), nf, L.ptr(label, i32), L.stream())
     return label
+
+
+def kept_after_quirk(counts, any_miss, num_com_vis=2):
+    """The `values[1:]` of both cleaning scripts (clean_mesh.py:80-90 with num_com_vis = 1, clean_meshes.py:248-260) on device tensors:
+    counts (F,) views that hit each face first, any_miss (nv,) -> (keep (F,) bool, len(values)).  values = the sorted faces with counts >=
+    num_com_vis, with -1 in front if at least num_com_vis views had a miss; values[1:] is kept."""
+    keep = counts >= num_com_vis
+    n_values = int(keep.sum())
+    if int((any_miss > 0).sum()) >= num_com_vis:
+        return keep, n_values + 1               # values[0] is the -1 of the misses
+    hit = torch.nonzero(keep).reshape(-1)
+    if len(hit):
+        keep = keep.clone()
+        keep[hit[0]] = False                    # values[1:] drops the smallest hit face instead
+    return keep, n_values
+
+
+def large_components(v_np, t_dtype, t, min_faces):
+    """The tail of both cleaning scripts (clean_mesh.py:101-106, clean_meshes.py:268-281) on device triangles t (F,3) int64 over the host
+    vertices v_np: the components of at least `min_faces` faces by trimesh's rule (a face without a neighbour across an edge of exactly
+    two faces is in no component), then the referenced vertices in their order -> (vertices, triangles of t_dtype) numpy."""
+    dev, n_v = t.device, len(v_np)
+    if len(t):
+        pairs = face_adjacency(t, n_v)
+        label = face_components(t, n_v, pairs).long()
+        in_graph = torch.zeros(len(t), device=dev, dtype=torch.bool)
+        in_graph[pairs.reshape(-1).long()] = True
+        t = t[in_graph & (torch.bincount(label, minlength=len(t))[label] >= min_faces)]
+    used = torch.zeros(n_v, device=dev, dtype=torch.bool)
+    used[t.reshape(-1)] = True
+    remap = torch.cumsum(used, 0) - 1
+    return v_np.reshape(-1, 3)[used.cpu().numpy()], remap[t].cpu().numpy().astype(t_dtype)
 
 
 __all__ = [n_ for n_ in dir() if not n_.startswith("__")]      # private helpers travel too: the package namespace is the old module's

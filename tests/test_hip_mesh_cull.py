@@ -270,6 +270,52 @@ def test_values_quirk_drops_the_smallest_face_when_every_masked_ray_hits():
     assert int(any_miss.item()) == 0 and flags.sum() > 100
 
 
+def _axis_views():
+    """Three 48 x 64 views of the origin from 3 units away.  Focal length 64 and principal point (31.5, 23.5): every entry of K^-1 is a
+    dyadic rational, so inverting the 4x4 and inverting its 3x3 block give the same bits (asserted where it is used)."""
+    intr = torch.tensor([[64.0, 0, 31.5, 0], [0, 64.0, 23.5, 0], [0, 0, 1, 0], [0, 0, 0, 1]])
+    c2ws = []
+    for rot in (torch.eye(3), torch.tensor([[0.0, 0, 1], [0, 1, 0], [-1, 0, 0]]),
+                torch.tensor([[np.cos(0.5), 0, np.sin(0.5)], [0, 1, 0], [-np.sin(0.5), 0, np.cos(0.5)]], dtype=torch.float32)):
+        c2w = torch.eye(4)
+        c2w[:3, :3] = rot
+        c2w[:3, 3] = -3.0 * rot[:, 2]
+        c2ws.append(c2w)
+    return intr.repeat(3, 1, 1), torch.stack(c2ws)
+
+
+@pytest.mark.parametrize("radii,misses", [((18, 18, 8), [1, 1, 0]), ((8, 8, 8), [0, 0, 0])])
+def test_one_view_ray_kernel_serves_both_cleaners_bit_for_bit(radii, misses):
+    """The two instantiations of the view-ray kernel on one scene: K23's (float masks > 0, upscale 1, no advance, one row of flags) marks
+    the union of what K25's (uint8 masks > 128, dep_min = 0, one row per view) marks per view, the miss flags agree, and `values[1:]` with
+    num_com_vis = 1 on K25's outputs keeps the faces io.clean_mesh_outside_frustum keeps.  A 0.6 sphere (silhouette radius 13 pixels) and
+    a detached floater on a 32^3 lattice; centred disk masks of `radii` pixels: 18 reaches past the silhouette (rays miss), 8 does not
+    (no ray misses: the smallest hit face is the one dropped, on both paths)."""
+    from gens_amd import io, ops
+    a, b = _sphere((0.02, -0.01, 0.03), 0.6), _sphere((0.0, 0.85, 0.0), 0.08)
+    v, t = _mc(lambda x, y, z: torch.minimum(a(x, y, z), b(x, y, z)), 32)
+    intrs, c2ws = _axis_views()
+    assert torch.equal(ops.view_ray_cams(intrs, c2ws, "4x4"), ops.view_ray_cams(intrs, c2ws, "3x3"))
+    yy, xx = torch.meshgrid(torch.arange(48.0), torch.arange(64.0), indexing="ij")
+    mask_float = torch.stack([0.25 * ((xx - 31.5) ** 2 + (yy - 23.5) ** 2 < r * r).float() for r in radii])
+    mask_u8 = (255 * (mask_float > 0)).to(torch.uint8)
+    grid = ops.build_mesh_grid(torch.from_numpy(v).to(DEV), torch.from_numpy(t).to(DEV))
+    flags23, miss23 = ops.visible_faces(grid, mask_float, intrs, c2ws, upscale=1)
+    counts, flags25, miss25 = ops.view_rays_hit_counts(grid, mask_u8, intrs, c2ws, dep_min=0)
+    assert flags25.shape == (3, len(t)) and flags25.dtype == flags23.dtype == torch.uint8
+    assert torch.equal(flags23, flags25.amax(0)) and torch.equal(counts, flags25.sum(0, dtype=torch.int32))
+    assert miss25.cpu().tolist() == misses and int(miss23.item()) == int(any(misses))
+    assert all(int(f.sum()) > 50 for f in flags25)
+    keep, n_values = ops.kept_after_quirk(counts, miss25, 1)
+    assert torch.equal(keep, ops.kept_after_quirk(flags23, miss23, 1)[0])          # what clean_mesh_outside_frustum hands its component step
+    hit = torch.nonzero(flags23).reshape(-1)
+    dropped = torch.nonzero(flags23.bool() & ~keep).reshape(-1).cpu().tolist()
+    assert dropped == ([] if any(misses) else [int(hit[0])]) and n_values == len(hit) + int(any(misses))
+    want = ops.large_components(v, t.dtype, torch.from_numpy(t).to(DEV)[keep], 1)
+    _assert_same_mesh(io.clean_mesh_outside_frustum(v, t, mask_float, intrs, c2ws, upscale=1, min_faces=1), want)
+    assert len(want[1]) > 100
+
+
 def test_save_validation_outputs_with_and_without_the_frustum_step(tmp_path):
     from gens_amd import io, synthetic
     v, t = _blobs()
