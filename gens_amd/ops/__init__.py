@@ -11,6 +11,7 @@ is what it was when ops was one module:
     ops.lookup    K2 / K2'' (lookup_volume with first and second derivatives), K3 (nearest masks, ray points), K4 (lookup_feature).
     ops.rays      K5-K7 (hierarchical sampling), K8 (compositing and the step-boundary kernels around it), K9 (patch reads, surface patch warp), K10 (TV).
     ops.geometry  K11 (lattice points), K12 (iso-surface extraction on the device), K23 / K25's view rays, face components and culling tail.
+    ops.sdf_pack  The weight streams of K6 and K7: slot tables, the gather, the four SDF stream orders (host code, no launch).
     ops.sdf       K6 (the fused SDF network in inference) and K17 (the SDF network of a training step).
     ops.gemm      K14: a^T b for tall operands, the weight-gradient product of the training step.
     ops.conv3d    K15 / K16: the 3 x 3 x 3 convolutions and the instance norm + ReLU of the cost-volume U-Net.

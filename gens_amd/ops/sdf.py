@@ -1,373 +1,12 @@
-"""K6 (the fused SDF network in inference) and K17 (the SDF network of a training step).
+"""K6 (the fused SDF network in inference) and K17 (the SDF network of a training step).  K6's weight streams: ops/sdf_pack.py.
 
 Part of gens_amd.ops (see ops/__init__.py); citations are relative to /root/reference."""
 from .base import *  # noqa: F401,F403
+from .sdf_pack import *  # noqa: F401,F403
 
 # ------------------------------------------------------------------------------------------------------------------
 # K6  fused SDF network (inference): look-up + encodings + 7 layers on fp32 MFMA (+ d sdf/dx)   (sdf_network.py:98-146)
 # ------------------------------------------------------------------------------------------------------------------
-def _pack_b_fragments(w):
-    """(J, K) matrix -> MFMA 32x32x2 B fragments [ceil(J/32)][ceil(K/2)][64]: lane l of fragment (nt, kk) holds
-    w[32 nt + (l & 31)][2 kk + (l >> 5)] (zero padded), so one B operand is one contiguous 256-B load."""
-    j, k = w.shape
-    nt, kk = (j + 31) // 32, (k + 1) // 2
-    wp = torch.zeros(nt * 32, kk * 2, device=w.device, dtype=_f32)
-    wp[:j, :k] = w
-    return wp.view(nt, 32, kk, 2).permute(0, 2, 3, 1).contiguous()
-
-
-def _pack_b_groups(w):
-    """(J, K) matrix -> grouped fp32 MFMA B stream for gens_sdf_mlp: [ceil(J/32)][ceil(K/8)][64][4]; lane l of group
-    (nt, g) holds w[32 nt + (l & 31)][8 g + 4 (l >> 5) + 0..3] (zero padded): one global_load_dwordx4 feeds 4 MFMAs."""
-    j, k = w.shape
-    nt, g = (j + 31) // 32, (k + 7) // 8
-    wp = torch.zeros(nt * 32, g * 8, device=w.device, dtype=_f32)
-    wp[:j, :k] = w
-    return wp.view(nt, 32, g, 2, 4).permute(0, 2, 3, 1, 4).contiguous()
-
-
-def _pack_b16(w, groups):
-    """(J <= 16, K) matrix -> B stream of a narrow layer for two 16x16x4 fp32 MFMA tiles (k7_blend.hip::narrow_group): for every group
-    (k0, S) of 4 S reduction columns, 64 lanes x S floats; lane l holds w[l % 16][k0 + S (l // 16) + 0..S-1] (zero padded)."""
-    j, k = w.shape
-    assert j <= 16
-    kmax = max(k0 + 4 * s for k0, s in groups)
-    wp = torch.zeros(16, kmax, device=w.device, dtype=_f32)
-    wp[:j, :k] = w
-    parts = []
-    for k0, s in groups:
-        blk = wp[:, k0:k0 + 4 * s].reshape(16, 4, s)           # [j][q][s]
-        parts.append(blk.permute(1, 0, 2).reshape(-1))         # lane = q * 16 + j
-    return torch.cat(parts).contiguous()
-
-
-def _value_slots(n_levels):
-    """Which input column every B-operand slot of k6v_sdf_value_f16.hip carries: three tables of shape (blocks, half, 8) holding a column
-    number, -1 for the constant-one slot and -2 for a zero slot.  Hidden blocks: the accumulator layout of the previous layer (lane half h,
-    register r of tile t = feature 32 t + 8 (r >> 2) + 4 h + (r & 3) = slot r & 7 of block 2 t + (r >> 3)).  Point encoding: half 0 holds
-    pe[0:15] and the one, half 1 pe[15:27].  Volume features: half 0 the channels of the levels below the middle one and its first two, half
-    1 the levels above and its last two; five encodings per channel (column e * CF + channel, sdf_network.py:104-107), then the one."""
-    cf = 4 * n_levels
-    nch, mid = cf // 2, n_levels // 2
-    nc = (5 * nch + 1 + 7) // 8
-    hid = torch.tensor([[[32 * (b >> 1) + 16 * (b & 1) + 8 * (s >> 2) + 4 * h + (s & 3) for s in range(8)] for h in range(2)] for b in range(8)])
-    pe = torch.full((2, 2, 8), -2, dtype=torch.long)
-    for q in range(16):
-        pe[q >> 3, 0, q & 7] = q if q < 15 else -1
-        if q < 12:
-            pe[q >> 3, 1, q & 7] = 15 + q
-    cond = torch.full((nc, 2, 8), -2, dtype=torch.long)
-    odd = n_levels % 2
-    for h in range(2):
-        nfull = 4 * mid                                       # whole levels of a half: the first / the last n_levels // 2
-        for lc in range(nch):
-            ch = (lc if h == 0 else 4 * (mid + odd) + lc) if lc < nfull else 4 * mid + 2 * h + (lc - nfull)
-            for e in range(5):
-                q = 5 * lc + e
-                cond[q >> 3, h, q & 7] = e * cf + ch
-    cond[(5 * nch) >> 3, 0, (5 * nch) & 7] = -1
-    return hid, pe, cond
-
-
-def _pack_value_units(ws, bs, n_levels):
-    """The weight stream and the output row of gens_sdf_value_f16 (layout and scaling: k6v_sdf_value_f16.hip's header).  ws[l] (out_l, in_l)
-    and bs[l] are the effective float32 weights of lin0..lin6.  Returns (units (U, 4, 2, 64, 8) float16, w_out (2, 64 + 8 NC) float32,
-    largest magnitude handed to half precision)."""
-    dev = ws[0].device
-    c = 100.0 / math.log(2.0)
-    r2 = 1.0 / math.sqrt(2.0)
-    hid, pe, cond = (t.to(dev) for t in _value_slots(n_levels))
-    fe = 20 * n_levels
-
-    def block_units(aug, table, offset):
-        """aug: (128, K + 2) with the bias in column K and zeros in column K + 1; table entries index aug[:, offset + entry]."""
-        k = aug.shape[1] - 2
-        cols = torch.where(table >= 0, table + offset, torch.where(table == -1, torch.full_like(table, k), torch.full_like(table, k + 1)))
-        g = aug[:, cols.reshape(-1)].reshape(4, 32, *table.shape)               # [tile][m][block][half][slot]
-        return g.permute(2, 0, 3, 1, 4).reshape(table.shape[0], 4, 64, 8)        # [block][tile][lane = 32 half + m][slot]
-
-    units = []
-    zero = torch.zeros(128, 1, device=dev, dtype=_f32)
-    for l in range(6):
-        w = torch.zeros(128, ws[l].shape[1], device=dev, dtype=_f32)
-        w[:ws[l].shape[0]] = ws[l]
-        b = torch.zeros(128, 1, device=dev, dtype=_f32)
-        b[:bs[l].shape[0], 0] = bs[l]
-        if l == 0:
-            units.append(block_units(torch.cat([c * w, c * b, zero], 1), pe, 0))
-            continue
-        h = w[:, :128].clone()
-        if l == 3:                                                               # x = cat([h[:101], pe]) / sqrt(2)   (sdf_network.py:111-112)
-            skip = torch.cat([c * r2 * w[:, 101:128], zero, zero], 1)            # the one slot of the point encoding carries nothing here
-            h = r2 * h
-            h[:, 101:] = 0.0
-        aug = torch.cat([h, c * w[:, 128:], c * b, zero], 1)
-        units.append(block_units(aug, hid, 0))
-        if l == 3:
-            units.append(block_units(skip, torch.where(pe == -1, torch.full_like(pe, -2), pe), 0))
-        units.append(block_units(aug, cond, 128))
-    units = torch.cat(units, 0)
-    pad = (-units.shape[0]) % 4                                                  # whole chunks of four units
-    if pad:
-        units = torch.cat([units, torch.zeros(pad, *units.shape[1:], device=dev, dtype=_f32)], 0)
-    hi = units.half()
-    lo = (units - hi.float()).half()
-    stream = torch.stack([hi, lo], 2).contiguous()                               # [unit][tile][hi, lo][lane][slot]
-    w_last = ws[6][0]
-    nc = cond.shape[0]
-    w_out = torch.zeros(2, 64 + 8 * nc, device=dev, dtype=_f32)
-    for hh in range(2):
-        feat = torch.tensor([32 * t + 8 * (r >> 2) + 4 * hh + (r & 3) for t in range(4) for r in range(16)], device=dev)
-        w_out[hh, :64] = w_last[feat] / c
-        tb = cond[:, hh].reshape(-1)
-        w_out[hh, 64:] = torch.where(tb >= 0, w_last[(128 + tb).clamp(0, 127 + fe)], torch.zeros_like(tb, dtype=_f32))
-    return stream, w_out, float(units.abs().max())
-
-
-def _value_pairs(n_levels):
-    """Slot tables of k6t_sdf_value.hip, (groups, half, 4) each (column number, -1 = the constant one, -2 = zero): an MFMA of group g,
-    position i multiplies the weights of the two columns [g, 0, i] and [g, 1, i] with what the two lane halves hold.  Hidden groups
-    (t, g'): columns 32 t + 8 g' + 4 half + i (the accumulator layout).  Point encoding: half 0 pe[0:15], half 1 pe[15:27] and the one.
-    Volume features: as gens_amd.ops._value_slots, 5 encodings per channel of the half, then the one (half 0)."""
-    cf = 4 * n_levels
-    nch, mid = cf // 2, n_levels // 2
-    gc = (5 * nch + 1 + 3) // 4
-    hid = torch.tensor([[[32 * t + 8 * g + 4 * h + i for i in range(4)] for h in range(2)] for t in range(4) for g in range(4)])
-    pe = torch.full((4, 2, 4), -2, dtype=torch.long)
-    for q in range(15):
-        pe[q >> 2, 0, q & 3] = q
-        pe[q >> 2, 1, q & 3] = 15 + q if q < 12 else (-1 if q == 12 else -2)
-    cond = torch.full((gc, 2, 4), -2, dtype=torch.long)
-    odd = n_levels % 2                                        # an odd level count: the middle level is shared, two channels per lane half
-    for h in range(2):
-        nfull = 4 * mid                                       # whole levels of a half: the first / the last n_levels // 2 (k6t_sdf_value.hip)
-        for lc in range(nch):
-            ch = (lc if h == 0 else 4 * (mid + odd) + lc) if lc < nfull else 4 * mid + 2 * h + (lc - nfull)
-            for e in range(5):
-                q = 5 * lc + e
-                cond[q >> 2, h, q & 3] = e * cf + ch
-    cond[(5 * nch) >> 2, 0, (5 * nch) & 3] = -1
-    return hid, pe, cond
-
-
-def _pack_value_stream(ws, bs, n_levels):
-    """The float32 weight stream and output row of gens_sdf_value (k6t_sdf_value.hip): per group of four feature pairs and output tile
-    T one float4 per lane (m, half) = the weights of row 32 T + m for the group's four columns of that half; columns fed by unscaled
-    inputs carry 100 / ln 2 (pre-scaled hidden units), layer 3's hidden columns 1 / sqrt(2), its skip columns both; one zero group is
-    appended because the kernel requests the next group before it knows there is none.  -> (stream (NG + 1, 4, 64, 4), w_out)."""
-    dev = ws[0].device
-    c = 100.0 / math.log(2.0)
-    r2 = 1.0 / math.sqrt(2.0)
-    hid, pe, cond = (t.to(dev) for t in _value_pairs(n_levels))
-    fe = 20 * n_levels
-
-    def groups(aug, table, offset):
-        k = aug.shape[1] - 2
-        cols = torch.where(table >= 0, table + offset, torch.where(table == -1, torch.full_like(table, k), torch.full_like(table, k + 1)))
-        g = aug[:, cols.reshape(-1)].reshape(4, 32, *table.shape)               # [tile][m][group][half][i]
-        return g.permute(2, 0, 3, 1, 4).reshape(table.shape[0], 4, 64, 4)        # [group][tile][lane = 32 half + m][i]
-
-    out = []
-    zero = torch.zeros(128, 1, device=dev, dtype=_f32)
-    for l in range(6):
-        w = torch.zeros(128, ws[l].shape[1], device=dev, dtype=_f32)
-        w[:ws[l].shape[0]] = ws[l]
-        b = torch.zeros(128, 1, device=dev, dtype=_f32)
-        b[:bs[l].shape[0], 0] = bs[l]
-        if l == 0:
-            out.append(groups(torch.cat([c * w, c * b, zero], 1), pe, 0))
-            continue
-        h = w[:, :128].clone()
-        if l == 3:                                                               # x = cat([h[:101], pe]) / sqrt(2)   (sdf_network.py:111-112)
-            skip = torch.cat([c * r2 * w[:, 101:128], zero, zero], 1)
-            h = r2 * h
-            h[:, 101:] = 0.0
-        aug = torch.cat([h, c * w[:, 128:], c * b, zero], 1)
-        out.append(groups(aug, hid if l != 3 else hid[:13], 0))                  # layer 3 reads features 0..103 only
-        if l == 3:
-            out.append(groups(skip, torch.where(pe == -1, torch.full_like(pe, -2), pe), 0))
-        out.append(groups(aug, cond, 128))
-    out.append(torch.zeros(1, 4, 64, 4, device=dev, dtype=_f32))
-    stream = torch.cat(out, 0).contiguous()
-    w_last = ws[6][0]
-    w_out = torch.zeros(2, 64 + 4 * cond.shape[0], device=dev, dtype=_f32)
-    for hh in range(2):
-        feat = torch.tensor([32 * t + 8 * (r >> 2) + 4 * hh + (r & 3) for t in range(4) for r in range(16)], device=dev)
-        w_out[hh, :64] = w_last[feat] / c
-        tb = cond[:, hh].reshape(-1)
-        w_out[hh, 64:] = torch.where(tb >= 0, w_last[(128 + tb).clamp(0, 127 + fe)], torch.zeros_like(tb, dtype=_f32))
-    return stream, w_out
-
-
-def _pack_grad_stream(ws, bs, n_levels):
-    """The weight stream and output row of gens_sdf_grad (k6g_sdf_grad.hip): the forward groups of _pack_value_stream, then the reverse
-    pass on the TRUE (unscaled) transposed matrices, layer 5 down to 1: 16 groups (layer 2: 13) of W_l[:, :128]^T for the hidden-unit
-    gradients, then per pair of conditioning tiles 8 groups (layer 2: 7) of 2 tiles x 8 pairs whose ROWS are ordered so that lane half h,
-    register r of tile c receives the gradient of that half's slot 16 c + r, at layer 3 four groups of 1 tile x 16 pairs for the
-    point-encoding slots, and after layer 1 the same four groups of W_0^T; two trailing zero groups (the kernel reads two groups ahead)."""
-    dev = ws[0].device
-    r2 = 1.0 / math.sqrt(2.0)
-    c = 100.0 / math.log(2.0)
-    hid, pe, cond = (t.to(dev) for t in _value_pairs(n_levels))
-    nch = 2 * n_levels
-    tc = ((5 * nch + 15) // 16 + 1) // 2 * 2                 # conditioning-gradient tiles, in pairs (k6g_sdf_grad.hip: GradShapeT::TC)
-    fwd, _ = _pack_value_stream(ws, bs, n_levels)
-    out = [fwd[:-1]]
-
-    def groups(mat, table):
-        """mat (32 NT, 128): rows = output rows of NT tiles, columns = hidden units of the layer -> (G, NT, 64, 4)."""
-        nt = mat.shape[0] // 32
-        g = mat[:, table.reshape(-1)].reshape(nt, 32, *table.shape)
-        return g.permute(2, 0, 3, 1, 4).reshape(table.shape[0], nt, 64, 4)
-
-    # accumulator row m of a tile <-> (lane half, register): m = 8 (r >> 2) + 4 half + (r & 3)
-    m = torch.arange(32, device=dev)
-    row_half, row_reg = (m >> 2) & 1, ((m >> 3) << 2) | (m & 3)
-    cond_flat = cond.permute(1, 0, 2).reshape(2, -1)                     # [half][slot] -> feature column, -1 one, -2 nothing
-    pe_flat = pe.permute(1, 0, 2).reshape(2, -1)
-    for l in range(5, 0, -1):
-        w = torch.zeros(128, ws[l].shape[1], device=dev, dtype=_f32)
-        w[:ws[l].shape[0]] = ws[l]
-        wt = w[:, :128].t().clone()                                       # rows: hidden inputs, columns: units of layer l
-        if l == 3:
-            wt = r2 * wt
-            wt[101:] = 0.0
-        out.append(groups(wt, hid if l != 2 else hid[:13]).reshape(-1, 4, 64, 4))
-        mc = torch.zeros(32 * tc, 128, device=dev, dtype=_f32)
-        for cc in range(tc):
-            slot = 16 * cc + row_reg
-            col = torch.where(slot < cond_flat.shape[1], cond_flat[row_half, slot.clamp(max=cond_flat.shape[1] - 1)], torch.full_like(slot, -2))
-            live = col >= 0
-            mc[32 * cc + m[live]] = w[:, 128 + col[live]].t()
-        full = groups(mc, hid)                                            # (16 = (t, g), tc, 64, 4)
-        for cc in range(0, tc, 2):
-            for t in range(4 if l != 2 else 3):
-                for gg in range(2):
-                    a, b = full[4 * t + 2 * gg], full[4 * t + 2 * gg + 1]
-                    out.append(torch.stack([a[cc], b[cc], a[cc + 1], b[cc + 1]])[None])
-            if l == 2:
-                a, b = full[12], full[13]
-                out.append(torch.stack([a[cc], b[cc], a[cc + 1], b[cc + 1]])[None])
-        if l == 3 or l == 1:
-            src = r2 * w[:, 101:128] if l == 3 else None
-            if l == 1:
-                w0 = torch.zeros(128, 27, device=dev, dtype=_f32)
-                w0[:ws[0].shape[0]] = ws[0]
-                src = w0
-            mp = torch.zeros(32, 128, device=dev, dtype=_f32)
-            col = torch.where(row_reg < pe_flat.shape[1], pe_flat[row_half, row_reg.clamp(max=pe_flat.shape[1] - 1)], torch.full_like(row_reg, -2))
-            live = col >= 0
-            mp[m[live]] = src[:, col[live]].t()
-            fp = groups(mp, hid)                                          # (16, 1, 64, 4)
-            out.append(fp[:, 0].reshape(4, 4, 64, 4))                     # group t: the four float4 g = 0..3
-    out.append(torch.zeros(2, 4, 64, 4, device=dev, dtype=_f32))
-    stream = torch.cat(out, 0).contiguous()
-    w_last = ws[6][0]
-    fe = 20 * n_levels
-    w_out = torch.zeros(2, 64 + 16 * tc, device=dev, dtype=_f32)
-    for hh in range(2):
-        feat = torch.tensor([32 * t + 8 * (r >> 2) + 4 * hh + (r & 3) for t in range(4) for r in range(16)], device=dev)
-        w_out[hh, :64] = w_last[feat] / c
-        tb = cond_flat[hh][:16 * tc]
-        w_out[hh, 64:64 + tb.shape[0]] = torch.where(tb >= 0, w_last[(128 + tb).clamp(0, 127 + fe)], torch.zeros_like(tb, dtype=_f32))
-    return stream, w_out
-
-
-def _pack_grad_pieces(ws, bs, n_levels, n_pieces=None, terms=2):
-    """The piece stream of gens_sdf_grad_f16 (k6gh_sdf_grad_f16.hip): 1 KB pieces = the A operand (hi or lo halfs) of one 32-row output
-    tile and one 16-deep K block, lane (m, kh) holding row m's weights for the eight reduction slots of lane half kh (_value_slots).
-    Forward: layer 0's two point-encoding K blocks, then per layer the conditioning K blocks, (layer 3: the point-encoding blocks,) the
-    eight hidden blocks -- the scaling of _pack_value_units, 4 tiles x {hi, lo} per block.  Reverse, on the TRUE transposed matrices,
-    layer 5 down to 1: per K block of G_l (layer 2: seven) the four hidden tiles, the conditioning tiles and at layer 3 the
-    point-encoding tile, rows ordered as in _pack_grad_stream; then the eight blocks of G_0 for the point-encoding tile.  Padded with
-    zeros to whole chunks of eight pieces.  -> (pieces (N, 64, 8) float16, largest magnitude handed to half precision).
-    terms=3: the stream of gens_sdf_value_bf16x3 / gens_sdf_grad_bf16x3 (k6b_sdf_bf16x3.hip) -- the same order with three round-to-nearest
-    bfloat16 terms (x0, x1, x2) per (block, tile) instead of (hi, lo): -> (pieces (N, 64, 8) bfloat16, largest magnitude)."""
-    dev = ws[0].device
-    c = 100.0 / math.log(2.0)
-    r2 = 1.0 / math.sqrt(2.0)
-    hid, pe, cond = (t.to(dev) for t in _value_slots(n_levels))
-    nch = 2 * n_levels
-    tc = (5 * nch + 15) // 16
-    zero = torch.zeros(128, 1, device=dev, dtype=_f32)
-
-    def blocks(mat, table):
-        """mat (32 NT, K + 2): column K = what the constant-one slot multiplies, column K + 1 zeros; table (B, 2, 8) of column numbers
-        (-1 the one, -2 nothing) -> (B, NT, 64, 8): block, tile, lane = 32 half + m, slot."""
-        nt, k = mat.shape[0] // 32, mat.shape[1] - 2
-        cols = torch.where(table >= 0, table, torch.where(table == -1, torch.full_like(table, k), torch.full_like(table, k + 1)))
-        g = mat[:, cols.reshape(-1)].reshape(nt, 32, *table.shape)                # [tile][m][block][half][slot]
-        return g.permute(2, 0, 3, 1, 4).reshape(table.shape[0], nt, 64, 8)
-
-    out = []
-    for l in range(6):
-        w = torch.zeros(128, ws[l].shape[1], device=dev, dtype=_f32)
-        w[:ws[l].shape[0]] = ws[l]
-        b = torch.zeros(128, 1, device=dev, dtype=_f32)
-        b[:bs[l].shape[0], 0] = bs[l]
-        if l == 0:
-            out.append(blocks(torch.cat([c * w, c * b, zero], 1), pe).reshape(-1, 64, 8))
-            continue
-        h = w[:, :128].clone()
-        if l == 3:                                                               # x = cat([h[:101], pe]) / sqrt(2)   (sdf_network.py:111-112)
-            h = r2 * h
-            h[:, 101:] = 0.0
-        out.append(blocks(torch.cat([c * w[:, 128:], c * b, zero], 1), cond).reshape(-1, 64, 8))
-        if l == 3:                                                               # (the one slot of the point encoding carries nothing here)
-            out.append(blocks(torch.cat([c * r2 * w[:, 101:128], zero, zero], 1), torch.where(pe == -1, torch.full_like(pe, -2), pe)).reshape(-1, 64, 8))
-        out.append(blocks(torch.cat([h, zero, zero], 1), hid).reshape(-1, 64, 8))
-    fwd = torch.cat(out, 0)                                                       # (units x 4 tiles, 64, 8)
-    # accumulator row m of a tile <-> (lane half, register): m = 8 (r >> 2) + 4 half + (r & 3)
-    m = torch.arange(32, device=dev)
-    row_half, row_reg = (m >> 2) & 1, ((m >> 3) << 2) | (m & 3)
-    cond_flat = cond.permute(1, 0, 2).reshape(2, -1)                              # [half][slot] -> feature column, -1 one, -2 nothing
-    pe_flat = pe.permute(1, 0, 2).reshape(2, -1)
-
-    def slot_rows(src, flat, n_tiles):
-        """(32 n_tiles, 128): row 32 c + m = src[:, column of slot 16 c + reg(m) of half(m)] (zero where the slot carries no column)."""
-        mat = torch.zeros(32 * n_tiles, 128, device=dev, dtype=_f32)
-        for cc in range(n_tiles):
-            slot = 16 * cc + row_reg
-            col = torch.where(slot < flat.shape[1], flat[row_half, slot.clamp(max=flat.shape[1] - 1)], torch.full_like(slot, -2))
-            live = col >= 0
-            mat[32 * cc + m[live]] = src[:, col[live]].t()
-        return mat
-
-    rev = []
-    zz = torch.zeros(1, 2, device=dev, dtype=_f32)
-    for l in range(5, 0, -1):
-        w = torch.zeros(128, ws[l].shape[1], device=dev, dtype=_f32)
-        w[:ws[l].shape[0]] = ws[l]
-        wt = w[:, :128].t().clone()                                               # rows: hidden inputs, columns: units of layer l
-        if l == 3:
-            wt = r2 * wt
-            wt[101:] = 0.0
-        rows = [wt, slot_rows(w[:, 128:], cond_flat, tc)]
-        if l == 3:
-            rows.append(slot_rows(r2 * w[:, 101:128], pe_flat, 1))
-        mat = torch.cat(rows, 0)
-        mat = torch.cat([mat, zz.expand(mat.shape[0], 2)], 1)
-        rev.append(blocks(mat, hid if l != 2 else hid[:7]).reshape(-1, 64, 8))  # [block][tile]
-    w0 = torch.zeros(128, 27, device=dev, dtype=_f32)
-    w0[:ws[0].shape[0]] = ws[0]
-    mat = slot_rows(w0, pe_flat, 1)
-    rev.append(blocks(torch.cat([mat, zz.expand(32, 2)], 1), hid).reshape(-1, 64, 8))
-    tiles = torch.cat([fwd] + rev, 0)                                             # one row per (block, tile)
-    if terms == 3:
-        parts, rest = [], tiles
-        for _ in range(3):                                                        # x - x0 and x - x0 - x1 are exact in float32
-            parts.append(rest.bfloat16())
-            rest = rest - parts[-1].float()
-    else:
-        hi = tiles.half()
-        parts = [hi, (tiles - hi.float()).half()]
-    pieces = torch.stack(parts, 1).reshape(-1, 64, 8)                             # [block][tile][hi, lo] / [x0, x1, x2]
-    pad = (-pieces.shape[0]) % 8 if n_pieces is None else n_pieces - pieces.shape[0]      # (whole chunks of the kernel's ring)
-    if pad:
-        pieces = torch.cat([pieces, torch.zeros(pad, 64, 8, device=dev, dtype=pieces.dtype)], 0)
-    return pieces.contiguous(), float(tiles.abs().max())
-
-
 class SdfMlpPlan:
     """Weights of an SDFNetwork re-packed for gens_sdf_mlp.  Only the shipped architecture is supported
     (`supported(net)`); anything else keeps using the PyTorch layers on top of the K2 look-up kernels."""
@@ -450,6 +89,36 @@ class SdfMlpPlan:
         return hit
 
 
+# What differs between the launches of the stream kernels: entry point -> (the plan's weight stream, its dtype, the plan's output row, whether
+# plan.grad_scale is passed, the stash of a gradient pass, whether the overflow word is passed).
+_SDF_STREAMS = {
+    "gens_sdf_grad_f16": ("grad_pieces", torch.float16, "grad_row", True, sdf_grad_f16_stash, True),
+    "gens_sdf_grad_bf16x3": ("bf16x3_pieces", torch.bfloat16, "grad_row", False, sdf_grad_f16_stash, False),
+    "gens_sdf_grad": ("grad_stream", _f32, "grad_row", False, sdf_grad_stash, False),
+    "gens_sdf_value_f16": ("value_units", torch.float16, "value_w_out", False, None, True),
+    "gens_sdf_value_bf16x3": ("bf16x3_pieces", torch.bfloat16, "grad_row", False, None, False),
+    "gens_sdf_value": ("value_stream", _f32, "value_row", False, None, False),
+}
+
+
+def _sdf_route(plan, want_grad, precision, kernels):
+    """(entry point, profile label) of a launch of sdf_mlp; no GPU involved.  In this order: the split-half kernel under precision "f16x2" if
+    the plan has its stream (weights inside the half range; the gradient pass also needs kernels.sdf_grad_f16) -- whatever kernels.sdf_value /
+    sdf_grad say; the three-term bfloat16 kernel under "bf16x3" if the plan has its pieces (3 and 5 levels); the float32 stream kernel under
+    "transposed" or "bf16x3"; else the row-major gens_sdf_mlp, whose two device kernels (sdf_mlp_k<FE, true / false>) are priced separately."""
+    kind = "grad" if want_grad else "value"
+    generation = kernels.sdf_grad if want_grad else kernels.sdf_value
+    if precision == "f16x2" and ((kernels.sdf_grad_f16 and getattr(plan, "grad_pieces", None) is not None) if want_grad else plan.value_ok):
+        entry = f"gens_sdf_{kind}_f16"
+    elif generation == "bf16x3" and getattr(plan, "bf16x3_pieces", None) is not None:
+        entry = f"gens_sdf_{kind}_bf16x3"
+    elif generation in ("transposed", "bf16x3"):
+        entry = f"gens_sdf_{kind}"
+    else:
+        return "gens_sdf_mlp", f"gens_sdf_mlp:{kind}"
+    return entry, entry
+
+
 def sdf_mlp(plan, volumes, pts, index=None, want_grad=False, sdf_out=None, grad_out=None, precision="f32", count=None):
     """sdf (and d sdf/dx) of pts[index] written to sdf_out[index] / grad_out[index] (fresh, densely indexed outputs if
     no buffers are given).  volumes: packed VolumeSet with 3 or 5 levels.  No autograd graph is built (inference).
@@ -469,48 +138,23 @@ def sdf_mlp(plan, volumes, pts, index=None, want_grad=False, sdf_out=None, grad_
     fe = 20 * plan.n_levels
     flops = 2 * (27 * 128 + (128 + fe) * (4 * 128 + 101 + 1)) * (2 if want_grad else 1)
     nbytes = n * (12 + (16 if want_grad else 4) + (8 if idx is not None else 0))
-    tag = ":grad" if want_grad else ":value"     # profile key: the two device kernels (sdf_mlp_k<FE, true / false>) are priced separately
-    if isinstance(plan, SdfTrainStep):           # this training step's streams (gens_sdf_train_pack): same layout, bias on the device
-        L.call("gens_sdf_mlp_dev", volumes.table, volumes.dim_table, volumes.n, plan.wf_table, plan.wb_table, L.ptr(plan.w_last),
-               L.ptr(plan.b_last), 1.0, L.ptr(pts), L.ptr(idx, torch.int64), n, L.ptr(count, torch.int32), L.ptr(sdf_out),
-               L.ptr(grad_out) if want_grad else None, L.stream(), nbytes=nbytes, flops=n * flops, live=None if count is None else (count, n),
-               label="gens_sdf_mlp" + tag)
-        return (sdf_out, grad_out) if want_grad else sdf_out
-    if want_grad and precision == "f16x2" and kernels.sdf_grad_f16 and getattr(plan, "grad_pieces", None) is not None:
-        L.call("gens_sdf_grad_f16", volumes.table, volumes.dim_table, volumes.n, L.ptr(plan.grad_pieces, torch.float16), L.ptr(plan.grad_row), plan.b_last,
-               plan.scale, plan.grad_scale, L.ptr(pts), L.ptr(idx, torch.int64), n, L.ptr(count, torch.int32), L.ptr(sdf_out), L.ptr(grad_out),
-               L.ptr(sdf_grad_f16_stash(pts.device), torch.uint8), L.ptr(plan.overflow, torch.int32), L.stream(),
-               nbytes=nbytes, flops=n * flops, live=None if count is None else (count, n), label="gens_sdf_grad_f16")
-    elif want_grad and kernels.sdf_grad == "bf16x3" and getattr(plan, "bf16x3_pieces", None) is not None:
-        # (under "f16x2" with weights out of the half range this pass takes the "f32" kernel)
-        L.call("gens_sdf_grad_bf16x3", volumes.table, volumes.dim_table, volumes.n, L.ptr(plan.bf16x3_pieces, torch.bfloat16), L.ptr(plan.grad_row),
-               plan.b_last, plan.scale, L.ptr(pts), L.ptr(idx, torch.int64), n, L.ptr(count, torch.int32), L.ptr(sdf_out), L.ptr(grad_out),
-               L.ptr(sdf_grad_f16_stash(pts.device), torch.uint8), L.stream(),
-               nbytes=nbytes, flops=n * flops, live=None if count is None else (count, n), label="gens_sdf_grad_bf16x3")
-    elif want_grad and kernels.sdf_grad in ("transposed", "bf16x3"):
-        # (under "f16x2" with weights out of the half range this pass stays float32; "bf16x3" at level counts other than 3 and 5)
-        L.call("gens_sdf_grad", volumes.table, volumes.dim_table, volumes.n, L.ptr(plan.grad_stream), L.ptr(plan.grad_row), plan.b_last,
-               plan.scale, L.ptr(pts), L.ptr(idx, torch.int64), n, L.ptr(count, torch.int32), L.ptr(sdf_out), L.ptr(grad_out),
-               L.ptr(sdf_grad_stash(pts.device), torch.uint8), L.stream(),
-               nbytes=nbytes, flops=n * flops, live=None if count is None else (count, n), label="gens_sdf_grad")
-    elif precision == "f16x2" and not want_grad and plan.value_ok:
-        L.call("gens_sdf_value_f16", volumes.table, volumes.dim_table, volumes.n, L.ptr(plan.value_units, torch.float16), L.ptr(plan.value_w_out),
-               plan.b_last, plan.scale, L.ptr(pts), L.ptr(idx, torch.int64), n, L.ptr(count, torch.int32), L.ptr(sdf_out),
-               L.ptr(plan.overflow, torch.int32), L.stream(), nbytes=nbytes, flops=n * flops, live=None if count is None else (count, n),
-               label="gens_sdf_value_f16")
-    elif not want_grad and kernels.sdf_value == "bf16x3" and getattr(plan, "bf16x3_pieces", None) is not None:
-        L.call("gens_sdf_value_bf16x3", volumes.table, volumes.dim_table, volumes.n, L.ptr(plan.bf16x3_pieces, torch.bfloat16), L.ptr(plan.grad_row),
-               plan.b_last, plan.scale, L.ptr(pts), L.ptr(idx, torch.int64), n, L.ptr(count, torch.int32), L.ptr(sdf_out), L.stream(),
-               nbytes=nbytes, flops=n * flops, live=None if count is None else (count, n), label="gens_sdf_value_bf16x3")
-    elif not want_grad and kernels.sdf_value in ("transposed", "bf16x3"):
-        L.call("gens_sdf_value", volumes.table, volumes.dim_table, volumes.n, L.ptr(plan.value_stream), L.ptr(plan.value_row), plan.b_last,
-               plan.scale, L.ptr(pts), L.ptr(idx, torch.int64), n, L.ptr(count, torch.int32), L.ptr(sdf_out), L.stream(), nbytes=nbytes,
-               flops=n * flops, live=None if count is None else (count, n), label="gens_sdf_value")
+    if isinstance(plan, SdfTrainStep):           # this training step's streams (gens_sdf_train_pack): the row-major layout, bias on the device
+        entry, label = "gens_sdf_mlp_dev", "gens_sdf_mlp:grad" if want_grad else "gens_sdf_mlp:value"
     else:
-        L.call("gens_sdf_mlp", volumes.table, volumes.dim_table, volumes.n, plan.wf_table, plan.wb_table, L.ptr(plan.w_last),
-               L.ptr(plan.w_last_scaled), plan.b_last, plan.scale, L.ptr(pts), L.ptr(idx, torch.int64), n, L.ptr(count, torch.int32), L.ptr(sdf_out),
-               L.ptr(grad_out) if want_grad else None, L.stream(), nbytes=nbytes, flops=n * flops, live=None if count is None else (count, n),
-               label="gens_sdf_mlp" + tag)
+        entry, label = _sdf_route(plan, want_grad, precision, kernels)
+    if entry in _SDF_STREAMS:
+        stream, dtype, row, scaled, stash, overflow = _SDF_STREAMS[entry]
+        operands = (L.ptr(getattr(plan, stream), dtype), L.ptr(getattr(plan, row)), plan.b_last, plan.scale) + ((plan.grad_scale,) if scaled else ())
+        tail = (L.ptr(grad_out), L.ptr(stash(pts.device), torch.uint8)) if want_grad else ()
+        if overflow:
+            tail += (L.ptr(plan.overflow, torch.int32),)
+    else:       # the row-major kernel and its _dev form
+        last = (L.ptr(plan.b_last), 1.0) if entry == "gens_sdf_mlp_dev" else (L.ptr(plan.w_last_scaled), plan.b_last, plan.scale)
+        operands = (plan.wf_table, plan.wb_table, L.ptr(plan.w_last), *last)
+        tail = (L.ptr(grad_out) if want_grad else None,)
+    L.call(entry, volumes.table, volumes.dim_table, volumes.n, *operands, L.ptr(pts), L.ptr(idx, torch.int64), n, L.ptr(count, torch.int32),
+           L.ptr(sdf_out), *tail, L.stream(), nbytes=nbytes, flops=n * flops, live=None if count is None else (count, n),
+           label=label)
     if not getattr(plan, "finite", True):
         _poison(idx, count, sdf_out, grad_out if want_grad else None)
     return (sdf_out, grad_out) if want_grad else sdf_out
