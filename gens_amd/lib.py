@@ -188,6 +188,7 @@ SIGNATURES = {
     "gens_dilate_u8": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _ip, _p],
     "gens_vertex_mask_votes": [_p, _l, _p, _p, _i, _i, _i, _p, _p],
     "gens_view_rays_hit_counts": [C.POINTER(MeshGridArgs), _p, _p, _i, _i, _i, _f, _p, _p, _p],
+    "gens_filter_masks": [_p, _f, _pp, _pp, _pp, _ip, _i, _p, _p, _p],
 }
 
 _lib = None

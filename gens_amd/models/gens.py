@@ -85,6 +85,9 @@ class GenS(nn.Module):
             self.mask_volmes = nn.ParameterList([])       # [sic] -- the reference's spelling is part of the checkpoint format
             self.features = nn.ParameterList([])
         self.implicit_surface = ImplicitSurface(confs["implicit_surface"])
+        thresh = confs.get("filter_thresh", None)               # optional: init_volumes filters the masks to the SDF band (filter_volume)
+        if thresh is not None:
+            self.filter_thresh = float(thresh)
 
     # -- optimiser / checkpoint plumbing (gens.py:32-61) --------------------------------------------------------
     def get_optim_params(self, lr_confs):
@@ -120,17 +123,57 @@ class GenS(nn.Module):
         return {"volumes": self.volumes, "mask_volmes": self.mask_volmes, "features": self.features,
                 "implicit_surface": self.implicit_surface.state_dict()}
 
-    def init_volumes(self, ipts):
-        """Per-scene fine-tuning: freeze the CNN outputs into parameters (gens.py:63-85)."""
+    _UNSET = object()
+    filter_thresh = None      # default of init_volumes' keyword: None = the visibility masks as they are (what the reference ships, gens.py:73)
+
+    def init_volumes(self, ipts, filter_thresh=_UNSET):
+        """Per-scene fine-tuning: freeze the CNN outputs into parameters (gens.py:63-85).  filter_thresh (default: the attribute
+        `self.filter_thresh`, itself None or the model conf's optional key of that name): a float runs `filter_volume` on the fresh volumes and
+        masks where gens.py:73 has its commented-out call, before they become parameters."""
+        if filter_thresh is GenS._UNSET:
+            filter_thresh = self.filter_thresh
         with torch.no_grad():
             features = self.feature_network(ipts["imgs"])
             volumes, mask_volmes = self.volume.agg_mean_var(features, ipts["intrs"], ipts["c2ws"], min_vis_view=1)
             volumes = self.reg_network(volumes)
+        if filter_thresh is not None:
+            mask_volmes = self.filter_volume(volumes, list(mask_volmes), float(filter_thresh))
         self.volumes = nn.ParameterList([nn.Parameter(v.detach(), requires_grad=True) for v in volumes])
         self.mask_volmes = nn.ParameterList([nn.Parameter(v.detach(), requires_grad=False) for v in mask_volmes])
         self.features = nn.ParameterList([nn.Parameter(f.detach(), requires_grad=False) for f in features])
+        if filter_thresh is not None:
+            for p, m in zip(self.mask_volmes, mask_volmes):      # (a Parameter is a new tensor object: the bit words filter_volume attached go with it)
+                hit = getattr(m, "_gens_bits", None)
+                if hit is not None and hit[0] == m._version:
+                    p._gens_bits = (p._version, hit[1])
         self.has_vol = True
         self._drop_captured_steps()
+
+    @torch.no_grad()
+    def filter_volume(self, volumes, mask_volmes, thresh=0.1):
+        """gens.py:87-122 (which the reference ships switched off, and which cannot run as written: :104 passes a third argument to
+        SDFNetwork.sdf): keep, in every level's mask, the voxels whose level-0 voxel (x << l, y << l, z << l) lies within one voxel of the band
+        |sdf| < thresh inside the unit sphere.  The SDF lattice takes whatever route the surface is set to (ImplicitSurface.sdf_grid, the
+        f16x2 overflow re-run included); band, dilation, pyramid and products are one call of gens_filter_masks, whose bit words travel with
+        the returned masks.  Prints the reference's three lines (the ratios as CPU float32 tensors, one read-back for both).  Like the
+        reference, a list passed as `mask_volmes` is filled with the results and returned."""
+        from .. import ops
+        print("Filtering sdf volume...")
+        masks = list(mask_volmes)
+        d0 = int(volumes[0].shape[-1])
+        ops.filter_mask_dims((d0, d0, d0), [m.shape for m in masks])        # refuse before the lattice is evaluated
+        dev = volumes[0].device
+        lo, hi = torch.tensor([-1.0, -1.0, -1.0], device=dev), torch.tensor([1.0, 1.0, 1.0], device=dev)
+        u = self.implicit_surface.sdf_grid([v.detach() for v in volumes], lo, hi, d0)
+        filtered, n_band, n_dilated = ops.filter_masks(u, masks, thresh)
+        counts = torch.stack([n_band, n_dilated]).cpu()
+        total = torch.tensor(float(d0) ** 3, dtype=torch.float32)
+        print("Survival ratio:", counts[0].to(torch.float32) / total)
+        print("Survival ratio after dilation:", counts[1].to(torch.float32) / total)
+        if isinstance(mask_volmes, list):
+            mask_volmes[:] = filtered
+            return mask_volmes
+        return filtered
 
     # -- forward (gens.py:124-157) ------------------------------------------------------------------------------
     def _reload_match(self, step):

@@ -58,7 +58,7 @@ const char* gens_last_error(void);
  *       Later additions that change no existing entry keep 12: gens_sdf_{value,grad}_bf16x3 + gens_sdf_bf16x3_pieces, and K23's
  *       gens_mesh_grid_{count,fill}, gens_ray_first_hit, gens_view_rays_hit_faces, gens_face_cc_{hook,compress}, and K24's
  *       gens_mesh_sample_{count,emit}, gens_point_grid_{count,fill}, gens_radius_downsample_round, gens_nearest_point, and K25's
- *       gens_dilate_u8, gens_vertex_mask_votes, gens_view_rays_hit_counts. */
+ *       gens_dilate_u8, gens_vertex_mask_votes, gens_view_rays_hit_counts, and K26's gens_filter_masks. */
 int gens_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -772,6 +772,23 @@ int gens_vertex_mask_votes(const double* points, int64_t n_points, const float* 
                            int32_t* votes, void* stream);
 int gens_view_rays_hit_counts(const gens_mesh_grid* grid, const uint8_t* masks, const float* cams, int nv, int h, int w, float dep_min,
                               uint8_t* flags, int32_t* any_miss, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * K26  GenS.filter_volume (gens.py:87-122): the mask pyramid restricted to a dilated band around the surface, two launches for all levels.
+ *   u (D0, D0, D0) float32, indexed [ix, iy, iz]: the level-0 lattice of -sdf on linspace(-1, 1, D0)^3 (ImplicitSurface.sdf_grid).
+ *   dims (n_levels) HOST ints with dims[l] == dims[0] >> l and dims[0] a multiple of 1 << (n_levels - 1); at most GENS_MAX_LEVELS levels
+ *   (GENS_ELIMIT beyond); dims[0]^3 < 2^31.  masks_in / masks_out: HOST arrays of device pointers to (D_l^3) floats indexed [x, y, z]
+ *   (in place is allowed: masks_out[l] == masks_in[l]); bits_out: HOST array of device pointers to ceil(D_l^3 / 32) uint32 words each, in
+ *   gens_pack_mask_bits' format.  band_words: scratch, ceil(D0^3 / 32) uint32 words (the band as bits, left there for the caller).
+ *   counts: two device int64, SET by the call: band voxels, band voxels after dilation.
+ *     band[i] = |u[i]| < thresh (a NaN: 0) and sqrt(x^2 + y^2 + z^2) < 1 in float32 at gens_lattice_points' coordinates;
+ *     dil     = the 3 x 3 x 3 maximum of band, neighbours outside the cube ignored (F.max_pool3d(band, 3, 1, 1));
+ *     out_l[x, y, z] = in_l[x, y, z] * dil[x << l, y << l, z << l] (a float product: the chain of nearest halvings picks, it does not pool);
+ *     bits_l = out_l > 0.
+ *   Every pointer must be non-null and 4-byte aligned, counts 8-byte aligned.  Arguments are checked before any launch.
+ * ---------------------------------------------------------------------------------------------------------- */
+int gens_filter_masks(const float* u, float thresh, const float* const* masks_in, float* const* masks_out, uint32_t* const* bits_out,
+                      const int* dims, int n_levels, uint32_t* band_words, int64_t* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K14  C (m x n) = A^T B for tall row-major operands A (k x m), B (k x n), k >> m, n: the weight-gradient product of the training
