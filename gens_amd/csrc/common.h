@@ -91,6 +91,35 @@ __device__ __forceinline__ float linspace_at(float start, float end, int steps, 
     return (i < steps / 2) ? start + step * (float)i : end - step * (float)(steps - 1 - i);
 }
 
+// Union-find on int32 parents shared by K23 (faces of a mesh) and K27 (voxels of a bit volume).
+__device__ __forceinline__ int32_t parent_load(int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// Root of x with path halving.  Every parent access is an agent-scope atomic: a plain load may be served from this CU's L1 and never see
+// another workgroup's hook, and a walk on a stale line need not end.  Parents only ever point to smaller indices, so the walk ends and the
+// halving stores (to non-roots only; hooks write roots only) cannot make a cycle.
+static __device__ int32_t find_halving(int32_t* parent, int32_t x) {
+    for (;;) {
+        const int32_t p = parent_load(parent + x);
+        if (p == x) return x;
+        const int32_t gp = parent_load(parent + p);
+        if (gp != p) __hip_atomic_store(parent + x, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        x = gp;
+    }
+}
+
+// Join the sets of a and b: the larger ROOT is hooked under the smaller, so a set's root is its smallest member whatever order the hooks land
+// in.  Each failed exchange means another thread hooked that root: at most as many retries in all as there are elements.
+static __device__ void gens_union_min(int32_t* parent, int32_t a, int32_t b) {
+    for (;;) {
+        a = find_halving(parent, a);
+        b = find_halving(parent, b);
+        if (a == b) return;
+        const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
+        int32_t expect = hi;
+        if (__hip_atomic_compare_exchange_strong(parent + hi, &expect, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+    }
+}
+
 // 4x4 row-major matrix times (x,y,z,1): full homogeneous result.
 __device__ __forceinline__ float4 mat4_point(const float* __restrict__ m, float x, float y, float z) {
     float4 r;

@@ -245,34 +245,12 @@ __global__ __launch_bounds__(256) void view_rays_k(gens_mesh_grid g, const MaskT
 }
 
 // ------------------------------------------------------------------------------------------------ components
-__device__ __forceinline__ int32_t parent_load(int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// Root of x with path halving.  Every parent access is an agent-scope atomic: a plain load may be served from this CU's L1 and never see
-// another workgroup's hook, and a walk on a stale line need not end.  Parents only ever point to smaller indices, so the walk ends and the
-// halving stores (to non-roots only; hooks write roots only) cannot make a cycle.
-__device__ int32_t find_halving(int32_t* parent, int32_t x) {
-    for (;;) {
-        const int32_t p = parent_load(parent + x);
-        if (p == x) return x;
-        const int32_t gp = parent_load(parent + p);
-        if (gp != p) __hip_atomic_store(parent + x, gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        x = gp;
-    }
-}
-
 __global__ __launch_bounds__(256) void cc_hook_k(const int32_t* __restrict__ pairs, int64_t n_pairs, int32_t* parent, int64_t n_faces) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n_pairs) return;
     int32_t a = pairs[2 * i], b = pairs[2 * i + 1];
     if (a < 0 || b < 0 || a >= n_faces || b >= n_faces) return;       // (the caller's pairs are face ids; nothing else is touched)
-    for (;;) {                  // each failed exchange means another thread hooked that root: at most n_faces retries in all
-        a = find_halving(parent, a);
-        b = find_halving(parent, b);
-        if (a == b) return;
-        const int32_t hi = a > b ? a : b, lo = a > b ? b : a;
-        int32_t expect = hi;
-        if (__hip_atomic_compare_exchange_strong(parent + hi, &expect, lo, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
-    }
+    gens_union_min(parent, a, b);
 }
 
 __global__ __launch_bounds__(256) void cc_compress_k(const int32_t* __restrict__ parent, int64_t n, int32_t* __restrict__ label) {

@@ -1,5 +1,6 @@
 // K26: GenS.filter_volume (gens.py:87-122) -- the mask pyramid restricted to a one-voxel dilation of the band |sdf| < thresh inside the unit
-// sphere.  Two launches for all levels:
+// sphere.  Two launches for all levels (gens_filter_masks; gens_filter_band and gens_filter_levels run one each, for a caller that edits the
+// band in between: K27's largest component):
 //   filter_band_k    one thread per level-0 voxel: the band decision, left as BITS (a wave's ballot = two words along z, gens_pack_mask_bits'
 //                    format) -- the 256^3 lattice becomes 2 MB that the second launch reads from L2 -- and the band count.
 //   filter_levels_k  one thread per voxel of EVERY level: the 3 x 3 x 3 maximum around the level-0 voxel (x << l, y << l, z << l) from nine
@@ -72,25 +73,23 @@ __global__ __launch_bounds__(FILTER_BLOCK) void filter_levels_k(FilterLevels lv,
     }
 }
 
-extern "C" int gens_filter_masks(const float* u, float thresh, const float* const* masks_in, float* const* masks_out, uint32_t* const* bits_out,
-                                 const int* dims, int n_levels, uint32_t* band_words, int64_t* counts, void* stream) {
-    GENS_CHECK_ARG(n_levels >= 1, GENS_EINVAL, "gens_filter_masks: n_levels = %d", n_levels);
-    GENS_CHECK_ARG(n_levels <= GENS_MAX_LEVELS, GENS_ELIMIT, "gens_filter_masks: %d levels, at most GENS_MAX_LEVELS = %d", n_levels, GENS_MAX_LEVELS);
-    GENS_CHECK_ARG(u && masks_in && masks_out && bits_out && dims && band_words && counts, GENS_EINVAL, "gens_filter_masks: null pointer");
+// The argument checks and the level table of the second launch; -> 0 or the error code.
+static int filter_levels_table(const char* who, const float* const* masks_in, float* const* masks_out, uint32_t* const* bits_out, const int* dims,
+                               int n_levels, FilterLevels& lv, unsigned& blocks) {
+    GENS_CHECK_ARG(n_levels >= 1, GENS_EINVAL, "%s: n_levels = %d", who, n_levels);
+    GENS_CHECK_ARG(n_levels <= GENS_MAX_LEVELS, GENS_ELIMIT, "%s: %d levels, at most GENS_MAX_LEVELS = %d", who, n_levels, GENS_MAX_LEVELS);
+    GENS_CHECK_ARG(masks_in && masks_out && bits_out && dims, GENS_EINVAL, "%s: null pointer", who);
     const int d0 = dims[0];
-    GENS_CHECK_ARG(d0 >= 1 && d0 <= 1024, GENS_EINVAL, "gens_filter_masks: dims[0] = %d, 1 to 1024 (32-bit voxel indices)", d0);
-    GENS_CHECK_ARG(d0 % (1 << (n_levels - 1)) == 0, GENS_EINVAL, "gens_filter_masks: dims[0] = %d is no multiple of 2^(n_levels - 1) = %d", d0,
+    GENS_CHECK_ARG(d0 >= 1 && d0 <= 1024, GENS_EINVAL, "%s: dims[0] = %d, 1 to 1024 (32-bit voxel indices)", who, d0);
+    GENS_CHECK_ARG(d0 % (1 << (n_levels - 1)) == 0, GENS_EINVAL, "%s: dims[0] = %d is no multiple of 2^(n_levels - 1) = %d", who, d0,
                    1 << (n_levels - 1));
-    GENS_CHECK_ARG(((uintptr_t)u & 3) == 0 && ((uintptr_t)band_words & 3) == 0 && ((uintptr_t)counts & 7) == 0, GENS_EINVAL,
-                   "gens_filter_masks: misaligned pointer (u, band_words: 4 bytes; counts: 8 bytes)");
-    FilterLevels lv;
     lv.n = n_levels;
-    unsigned blocks = 0;
+    blocks = 0;
     for (int l = 0; l < n_levels; ++l) {
-        GENS_CHECK_ARG(dims[l] == d0 >> l, GENS_EINVAL, "gens_filter_masks: dims[%d] = %d, expected dims[0] >> %d = %d", l, dims[l], l, d0 >> l);
-        GENS_CHECK_ARG(masks_in[l] && masks_out[l] && bits_out[l], GENS_EINVAL, "gens_filter_masks: null pointer at level %d", l);
+        GENS_CHECK_ARG(dims[l] == d0 >> l, GENS_EINVAL, "%s: dims[%d] = %d, expected dims[0] >> %d = %d", who, l, dims[l], l, d0 >> l);
+        GENS_CHECK_ARG(masks_in[l] && masks_out[l] && bits_out[l], GENS_EINVAL, "%s: null pointer at level %d", who, l);
         GENS_CHECK_ARG(((uintptr_t)masks_in[l] & 3) == 0 && ((uintptr_t)masks_out[l] & 3) == 0 && ((uintptr_t)bits_out[l] & 3) == 0, GENS_EINVAL,
-                       "gens_filter_masks: misaligned pointer at level %d", l);
+                       "%s: misaligned pointer at level %d", who, l);
         lv.in[l] = masks_in[l];
         lv.out[l] = masks_out[l];
         lv.bits[l] = bits_out[l];
@@ -99,15 +98,60 @@ extern "C" int gens_filter_masks(const float* u, float thresh, const float* cons
         blocks += gens_blocks((int64_t)dims[l] * dims[l] * dims[l], FILTER_BLOCK);
     }
     lv.first_block[n_levels] = blocks;
-    const int n0 = d0 * d0 * d0;
-    hipStream_t s = (hipStream_t)stream;
-    if (hipError_t e = hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), s)) {
+    return 0;
+}
+
+static int filter_clear(const char* who, int64_t* counts, int n, hipStream_t s) {
+    if (hipError_t e = hipMemsetAsync(counts, 0, n * sizeof(int64_t), s)) {
         (void)hipGetLastError();
-        gens_set_error("gens_filter_masks: clearing the counts: %s", hipGetErrorString(e));
+        gens_set_error("%s: clearing the counts: %s", who, hipGetErrorString(e));
         return (int)e;
     }
+    return 0;
+}
+
+extern "C" int gens_filter_masks(const float* u, float thresh, const float* const* masks_in, float* const* masks_out, uint32_t* const* bits_out,
+                                 const int* dims, int n_levels, uint32_t* band_words, int64_t* counts, void* stream) {
+    const char* who = "gens_filter_masks";
+    FilterLevels lv;
+    unsigned blocks;
+    if (int e = filter_levels_table(who, masks_in, masks_out, bits_out, dims, n_levels, lv, blocks)) return e;
+    GENS_CHECK_ARG(u && band_words && counts, GENS_EINVAL, "%s: null pointer", who);
+    GENS_CHECK_ARG(((uintptr_t)u & 3) == 0 && ((uintptr_t)band_words & 3) == 0 && ((uintptr_t)counts & 7) == 0, GENS_EINVAL,
+                   "%s: misaligned pointer (u, band_words: 4 bytes; counts: 8 bytes)", who);
+    const int d0 = dims[0], n0 = d0 * d0 * d0;
+    hipStream_t s = (hipStream_t)stream;
+    if (int e = filter_clear(who, counts, 2, s)) return e;
     filter_band_k<<<gens_blocks(n0, FILTER_BLOCK), FILTER_BLOCK, 0, s>>>(u, thresh, d0, n0, band_words, (unsigned long long*)counts);
     if (int e = gens_launch_status("gens_filter_masks (band)")) return e;
     filter_levels_k<<<blocks, FILTER_BLOCK, 0, s>>>(lv, band_words, (unsigned long long*)counts);
-    return gens_launch_status("gens_filter_masks");
+    return gens_launch_status(who);
+}
+
+extern "C" int gens_filter_band(const float* u, float thresh, int d0, uint32_t* band_words, int64_t* counts, void* stream) {
+    const char* who = "gens_filter_band";
+    GENS_CHECK_ARG(u && band_words && counts, GENS_EINVAL, "%s: null pointer", who);
+    GENS_CHECK_ARG(d0 >= 1 && d0 <= 1024, GENS_EINVAL, "%s: d0 = %d, 1 to 1024 (32-bit voxel indices)", who, d0);
+    GENS_CHECK_ARG(((uintptr_t)u & 3) == 0 && ((uintptr_t)band_words & 3) == 0 && ((uintptr_t)counts & 7) == 0, GENS_EINVAL,
+                   "%s: misaligned pointer (u, band_words: 4 bytes; counts: 8 bytes)", who);
+    const int n0 = d0 * d0 * d0;
+    hipStream_t s = (hipStream_t)stream;
+    if (int e = filter_clear(who, counts, 1, s)) return e;
+    filter_band_k<<<gens_blocks(n0, FILTER_BLOCK), FILTER_BLOCK, 0, s>>>(u, thresh, d0, n0, band_words, (unsigned long long*)counts);
+    return gens_launch_status(who);
+}
+
+extern "C" int gens_filter_levels(const float* const* masks_in, float* const* masks_out, uint32_t* const* bits_out, const int* dims, int n_levels,
+                                  const uint32_t* band_words, int64_t* counts, void* stream) {
+    const char* who = "gens_filter_levels";
+    FilterLevels lv;
+    unsigned blocks;
+    if (int e = filter_levels_table(who, masks_in, masks_out, bits_out, dims, n_levels, lv, blocks)) return e;
+    GENS_CHECK_ARG(band_words && counts, GENS_EINVAL, "%s: null pointer", who);
+    GENS_CHECK_ARG(((uintptr_t)band_words & 3) == 0 && ((uintptr_t)counts & 7) == 0, GENS_EINVAL,
+                   "%s: misaligned pointer (band_words: 4 bytes; counts: 8 bytes)", who);
+    hipStream_t s = (hipStream_t)stream;
+    if (int e = filter_clear(who, counts + 1, 1, s)) return e;
+    filter_levels_k<<<blocks, FILTER_BLOCK, 0, s>>>(lv, band_words, (unsigned long long*)counts);
+    return gens_launch_status(who);
 }

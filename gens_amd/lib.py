@@ -189,6 +189,11 @@ SIGNATURES = {
     "gens_vertex_mask_votes": [_p, _l, _p, _p, _i, _i, _i, _p, _p],
     "gens_view_rays_hit_counts": [C.POINTER(MeshGridArgs), _p, _p, _i, _i, _i, _f, _p, _p, _p],
     "gens_filter_masks": [_p, _f, _pp, _pp, _pp, _ip, _i, _p, _p, _p],
+    "gens_filter_band": [_p, _f, _i, _p, _p, _p],
+    "gens_filter_levels": [_pp, _pp, _pp, _ip, _i, _p, _p, _p],
+    "gens_components_scratch_bytes": [_i, _i, _i],          # (returns int64 bytes, not a status: load() sets its restype; call it through lib)
+    "gens_largest_component": [_p, _i, _i, _i, _i, _p, _p, _p, _p],
+    "gens_unpack_mask_bits": [_p, _l, _p, _p],
 }
 
 _lib = None
@@ -239,6 +244,7 @@ def load():
         fn = getattr(lib, name)
         fn.restype = _i
         fn.argtypes = args
+    lib.gens_components_scratch_bytes.restype = _l
     _lib = lib
     return lib
 

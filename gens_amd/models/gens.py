@@ -88,6 +88,9 @@ class GenS(nn.Module):
         thresh = confs.get("filter_thresh", None)               # optional: init_volumes filters the masks to the SDF band (filter_volume)
         if thresh is not None:
             self.filter_thresh = float(thresh)
+        keep = confs.get("filter_keep_largest", None)           # optional: filter_volume keeps only the band's largest region (clean_volume)
+        if keep is not None:
+            self.filter_keep_largest = bool(keep)
 
     # -- optimiser / checkpoint plumbing (gens.py:32-61) --------------------------------------------------------
     def get_optim_params(self, lr_confs):
@@ -125,11 +128,13 @@ class GenS(nn.Module):
 
     _UNSET = object()
     filter_thresh = None      # default of init_volumes' keyword: None = the visibility masks as they are (what the reference ships, gens.py:73)
+    filter_keep_largest = False   # read by filter_volume: True = only the band's largest 26-connected region survives (utils/tools.py:34-50)
 
-    def init_volumes(self, ipts, filter_thresh=_UNSET):
+    def init_volumes(self, ipts, filter_thresh=_UNSET, filter_keep_largest=_UNSET):
         """Per-scene fine-tuning: freeze the CNN outputs into parameters (gens.py:63-85).  filter_thresh (default: the attribute
         `self.filter_thresh`, itself None or the model conf's optional key of that name): a float runs `filter_volume` on the fresh volumes and
-        masks where gens.py:73 has its commented-out call, before they become parameters."""
+        masks where gens.py:73 has its commented-out call, before they become parameters.  filter_keep_largest (default: the attribute of that
+        name, itself False or the conf's key; an explicit False wins over both): the filter keeps only the band's largest region."""
         if filter_thresh is GenS._UNSET:
             filter_thresh = self.filter_thresh
         with torch.no_grad():
@@ -137,7 +142,9 @@ class GenS(nn.Module):
             volumes, mask_volmes = self.volume.agg_mean_var(features, ipts["intrs"], ipts["c2ws"], min_vis_view=1)
             volumes = self.reg_network(volumes)
         if filter_thresh is not None:
-            mask_volmes = self.filter_volume(volumes, list(mask_volmes), float(filter_thresh))
+            if filter_keep_largest is GenS._UNSET:
+                filter_keep_largest = self.filter_keep_largest
+            mask_volmes = self._filter_volume(volumes, list(mask_volmes), float(filter_thresh), bool(filter_keep_largest))
         self.volumes = nn.ParameterList([nn.Parameter(v.detach(), requires_grad=True) for v in volumes])
         self.mask_volmes = nn.ParameterList([nn.Parameter(v.detach(), requires_grad=False) for v in mask_volmes])
         self.features = nn.ParameterList([nn.Parameter(f.detach(), requires_grad=False) for f in features])
@@ -156,7 +163,16 @@ class GenS(nn.Module):
         |sdf| < thresh inside the unit sphere.  The SDF lattice takes whatever route the surface is set to (ImplicitSurface.sdf_grid, the
         f16x2 overflow re-run included); band, dilation, pyramid and products are one call of gens_filter_masks, whose bit words travel with
         the returned masks.  Prints the reference's three lines (the ratios as CPU float32 tensors, one read-back for both).  Like the
-        reference, a list passed as `mask_volmes` is filled with the results and returned."""
+        reference, a list passed as `mask_volmes` is filled with the results and returned.
+        The method keeps the reference's signature; with the attribute `self.filter_keep_largest` set (False by default, or the model conf's
+        optional key of that name; init_volumes has a keyword for it) the band is reduced to its largest 26-connected region before the
+        dilation -- utils/tools.py:34-50's clean_volume applied to the mask volume the threshold makes, on the device (ops.filter_masks,
+        keep_largest) -- and two more lines are printed after the reference's: clean_volume's `Num region: N` and a `Survival ratio` line for
+        the band that is kept."""
+        return self._filter_volume(volumes, mask_volmes, thresh, bool(self.filter_keep_largest))
+
+    @torch.no_grad()
+    def _filter_volume(self, volumes, mask_volmes, thresh, keep_largest):
         from .. import ops
         print("Filtering sdf volume...")
         masks = list(mask_volmes)
@@ -165,11 +181,17 @@ class GenS(nn.Module):
         dev = volumes[0].device
         lo, hi = torch.tensor([-1.0, -1.0, -1.0], device=dev), torch.tensor([1.0, 1.0, 1.0], device=dev)
         u = self.implicit_surface.sdf_grid([v.detach() for v in volumes], lo, hi, d0)
-        filtered, n_band, n_dilated = ops.filter_masks(u, masks, thresh)
-        counts = torch.stack([n_band, n_dilated]).cpu()
+        if keep_largest:
+            filtered, *found = ops.filter_masks(u, masks, thresh, keep_largest=True)
+        else:
+            filtered, *found = ops.filter_masks(u, masks, thresh)
+        counts = torch.stack(found).cpu()                 # band, dilated (, regions, kept)
         total = torch.tensor(float(d0) ** 3, dtype=torch.float32)
         print("Survival ratio:", counts[0].to(torch.float32) / total)
         print("Survival ratio after dilation:", counts[1].to(torch.float32) / total)
+        if keep_largest:
+            print("Num region:", int(counts[2]))
+            print("Survival ratio of the largest region:", counts[3].to(torch.float32) / total)
         if isinstance(mask_volmes, list):
             mask_volmes[:] = filtered
             return mask_volmes

@@ -19,7 +19,8 @@ is what it was when ops was one module:
     ops.conv2d    K21: the depth-wise 2-D convolutions of the MnasNet trunk.
     ops.points    K24: mesh sampling, radius down-sampling and capped nearest neighbours of the DTU scoring (evaluation/dtu_eval.py).
     ops.finalize  K25: elliptical dilation and vertex mask votes of the DTU mesh finalising (evaluation/clean_meshes.py).
-    ops.filter    K26: the mask pyramid restricted to the dilated SDF band (GenS.filter_volume, models/gens.py:87-122).
+    ops.filter    K26: the mask pyramid restricted to the dilated SDF band (GenS.filter_volume, models/gens.py:87-122);
+                  K27: the largest connected region of a mask volume (clean_volume, utils/tools.py:34-50).
 """
 from .base import *  # noqa: F401,F403
 from .volume import *  # noqa: F401,F403

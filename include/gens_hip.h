@@ -58,7 +58,8 @@ const char* gens_last_error(void);
  *       Later additions that change no existing entry keep 12: gens_sdf_{value,grad}_bf16x3 + gens_sdf_bf16x3_pieces, and K23's
  *       gens_mesh_grid_{count,fill}, gens_ray_first_hit, gens_view_rays_hit_faces, gens_face_cc_{hook,compress}, and K24's
  *       gens_mesh_sample_{count,emit}, gens_point_grid_{count,fill}, gens_radius_downsample_round, gens_nearest_point, and K25's
- *       gens_dilate_u8, gens_vertex_mask_votes, gens_view_rays_hit_counts, and K26's gens_filter_masks. */
+ *       gens_dilate_u8, gens_vertex_mask_votes, gens_view_rays_hit_counts, and K26's gens_filter_masks, gens_filter_band, gens_filter_levels,
+ *       and K27's gens_largest_component, gens_components_scratch_bytes, gens_unpack_mask_bits. */
 int gens_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -789,6 +790,35 @@ int gens_view_rays_hit_counts(const gens_mesh_grid* grid, const uint8_t* masks, 
  * ---------------------------------------------------------------------------------------------------------- */
 int gens_filter_masks(const float* u, float thresh, const float* const* masks_in, float* const* masks_out, uint32_t* const* bits_out,
                       const int* dims, int n_levels, uint32_t* band_words, int64_t* counts, void* stream);
+/* The two launches of gens_filter_masks one at a time, for a caller that edits the band in between (K27: keep its largest component).
+ *   gens_filter_band: the first launch.  SETS counts[0] (band voxels) and writes band_words; u, thresh, d0 = dims[0] as above.
+ *   gens_filter_levels: the second launch from the caller's band_words.  SETS counts[1] (band voxels after dilation) and leaves counts[0]
+ *   alone; everything else as above.  gens_filter_band followed by gens_filter_levels is gens_filter_masks. */
+int gens_filter_band(const float* u, float thresh, int d0, uint32_t* band_words, int64_t* counts, void* stream);
+int gens_filter_levels(const float* const* masks_in, float* const* masks_out, uint32_t* const* bits_out, const int* dims, int n_levels,
+                       const uint32_t* band_words, int64_t* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * K27  clean_volume (utils/tools.py:34-50: skimage.measure.label(mask, connectivity=3), regionprops, keep the largest region): the largest
+ *      connected component of a bit volume, six launches, nothing waits inside a launch.
+ *   bits_in / bits_out: ceil(nx * ny * nz / 32) uint32 words in gens_pack_mask_bits' format, bit (i & 31) of word (i >> 5) = voxel i in C
+ *   order of the (nx, ny, nz) volume; any positive extents with nx * ny * nz < 2^31 (GENS_ELIMIT beyond); bits past the last voxel are
+ *   ignored on input and zero on output; bits_out must not be bits_in.  connectivity: 3 (26 neighbours) or 1 (6 neighbours); a neighbour
+ *   outside the volume does not exist.  scratch: gens_components_scratch_bytes(nx, ny, nz) bytes, 8-byte aligned (16 bytes + one int32
+ *   parent per voxel: 67 MB at 256^3; 0 for extents the call refuses).
+ *     root of a set voxel = the smallest linear index of its component (a min-index union: the same whatever order the atomics land in);
+ *     winner = the component of largest size, a tie to the one whose first voxel comes first in C order (np.argmax over regionprops);
+ *     bits_out = the winner's voxels.
+ *   results: four device int64, SET by the call: the number of components; the winner's size; its root (-1 when the volume is empty); its
+ *   label number = 1 + the number of components whose first voxel precedes the winner's (skimage's and scipy's numbering; 0 when empty).
+ *   An empty volume gives empty bits_out and zero components.  Every pointer non-null; bits 4-byte, scratch and results 8-byte aligned.
+ *   Arguments are checked before any launch.
+ *   gens_unpack_mask_bits: the inverse of gens_pack_mask_bits, mask[i] = 1.0f or 0.0f for bit i, n >= 1 floats.
+ * ---------------------------------------------------------------------------------------------------------- */
+int64_t gens_components_scratch_bytes(int nx, int ny, int nz);
+int gens_largest_component(const uint32_t* bits_in, int nx, int ny, int nz, int connectivity, uint32_t* bits_out, void* scratch,
+                           int64_t* results, void* stream);
+int gens_unpack_mask_bits(const uint32_t* bits, int64_t n, float* mask, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K14  C (m x n) = A^T B for tall row-major operands A (k x m), B (k x n), k >> m, n: the weight-gradient product of the training

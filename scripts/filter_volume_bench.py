@@ -55,8 +55,9 @@ def quiet(fn):
         sys.stdout = real
 
 
-def steps_with_and_without(dims, iters, thresh=0.1):
-    """(iv): -> report lines."""
+def steps_with_and_without(dims, iters, thresh=0.1, configs=None, tag="(iv)"):
+    """(iv): -> report lines.  configs: (name, init_volumes keywords) pairs, the first one the base of the ratios (default: the visibility
+    masks against the filtered ones)."""
     from gens_amd import synthetic
     from gens_amd.config import gens_loss_conf, gens_model_conf
     from gens_amd.losses import Loss
@@ -76,7 +77,7 @@ def steps_with_and_without(dims, iters, thresh=0.1):
     all_o, all_d = synthetic.make_rays(sc["intrs"], sc["c2ws"], h, w)
     all_o, all_d = all_o.to(dev), all_d.to(dev)
     runs = {}
-    for name, kw in (("visibility masks", {}), (f"filter_thresh={thresh}", {"filter_thresh": thresh})):
+    for name, kw in configs or (("visibility masks", {}), (f"filter_thresh={thresh}", {"filter_thresh": thresh})):
         torch.manual_seed(0)
         model = GenS(gens_model_conf(volume_dims=tuple(dims))).to(dev).train()
         quiet(lambda: model.init_volumes({"imgs": imgs, "intrs": intrs, "c2ws": c2ws}, **kw))
@@ -119,10 +120,11 @@ def steps_with_and_without(dims, iters, thresh=0.1):
     out = []
     for name, r in runs.items():
         s, i = stats(r["step_ms"]), stats(r["image_ms"])
-        out.append(f"(iv) dims {tuple(dims)}, {name}: live share per level {[round(v, 4) for v in r['live']]}; fine-tune step {s[0]:.2f} ms ({s[1]:.2f} - {s[2]:.2f}); "
+        out.append(f"{tag} dims {tuple(dims)}, {name}: live share per level {[round(v, 4) for v in r['live']]}; fine-tune step {s[0]:.2f} ms ({s[1]:.2f} - {s[2]:.2f}); "
                    f"validation image 480 x 640 {i[0]:.1f} ms ({i[1]:.1f} - {i[2]:.1f})")
-    a, b = list(runs.values())
-    out.append(f"(iv) dims {tuple(dims)}: filtered / unfiltered = {stats(b['step_ms'])[0] / stats(a['step_ms'])[0]:.3f} (fine-tune step), "
+    (base, a), (last, b) = list(runs.items())[0], list(runs.items())[-1]
+    what = "filtered / unfiltered" if configs is None else f"{last} / {base}"
+    out.append(f"{tag} dims {tuple(dims)}: {what} = {stats(b['step_ms'])[0] / stats(a['step_ms'])[0]:.3f} (fine-tune step), "
                f"{stats(b['image_ms'])[0] / stats(a['image_ms'])[0]:.3f} (validation image)")
     for r in runs.values():
         r["model"].implicit_surface.join_speculation()
