@@ -1,0 +1,265 @@
+// K28: the two-level lattice of extract_geometry (implicit_surface.py:407-427) -- the SDF network evaluated near the iso-surface only.
+// res points per axis, bricks of `brick` cells; C = ceil((res - 1) / brick) + 1 coarse points per axis, coarse index i = fine index
+// min(i * brick, res - 1); (C - 1)^3 bricks, brick b between the coarse points b and b + 1 of every axis.  Six streaming launches around the
+// caller's evaluator (ops.sparse_lattice):
+//   coarse_points_k   the coarse lattice points, (n, 3) for the evaluator
+//   classify_k        one thread per brick: 8 corners of uc -> one byte (active: a corner non-finite, within margin of t, or the corners disagree)
+//   brick_points_k    the points of the listed point bricks, brick^3 each, (n, 3) for the evaluator
+//   fill_k            every fine point <- the lowest corner of its brick, four points along z per thread, one 16-byte store
+//   scatter_k         u[owned point] = -sdf for the evaluated bricks
+//   leaks_k           lattice edges that cross t with an endpoint in an inactive brick -> one int64
+// POINT BRICKS: fine index i belongs to point brick i / brick on each axis, P = ceil(res / brick) of them per axis.  P == C - 1 unless
+// (res - 1) % brick == 0; then the plane res - 1 is a point brick of its own (P == C), which the caller lists whenever the brick below it
+// is active -- so every list entry stands for exactly brick^3 evaluator rows, and a row whose index passes res - 1 is a clamped
+// duplicate that the scatter drops.  The brick that DECIDES for fine index i is min(i / brick, C - 2).
+// Coordinates are linspace_at's, K11's formula: the points are bit-equal to gens_lattice_points' at the same fine indices.
+// All indices are 32-bit (res^3 < 2^31, checked): the per-thread decode is a handful of 32-bit divisions, no 64-bit arithmetic.
+#include "common.h"
+
+#define SPARSE_BLOCK 256
+
+struct SparseBox { float lo[3], hi[3]; };
+
+struct SparseDims {
+    int res, brick, coarse, pbricks;      // R, B, C, P
+};
+
+static inline SparseDims sparse_dims(int res, int brick) {
+    SparseDims d;
+    d.res = res;
+    d.brick = brick;
+    d.coarse = (int)(((int64_t)res + brick - 2) / brick) + 1;
+    d.pbricks = (int)(((int64_t)res + brick - 1) / brick);
+    return d;
+}
+
+// The checks every entry point shares; -> 0 or the error code.
+static int sparse_check(const char* who, int res, int brick) {
+    GENS_CHECK_ARG(res >= 2, GENS_EINVAL, "%s: res = %d, at least 2 points per axis", who, res);
+    GENS_CHECK_ARG(brick >= 1, GENS_EINVAL, "%s: brick = %d, at least one cell", who, brick);
+    GENS_CHECK_ARG((int64_t)res * res * res < ((int64_t)1 << 31), GENS_ELIMIT, "%s: res = %d, res^3 must stay below 2^31 (32-bit point indices)", who, res);
+    return 0;
+}
+
+static int sparse_box(const char* who, const float* bmin3_host, const float* bmax3_host, SparseBox& b) {
+    GENS_CHECK_ARG(bmin3_host && bmax3_host, GENS_EINVAL, "%s: null pointer (bounds)", who);
+    for (int a = 0; a < 3; ++a) { b.lo[a] = bmin3_host[a]; b.hi[a] = bmax3_host[a]; }
+    return 0;
+}
+
+__global__ __launch_bounds__(SPARSE_BLOCK) void coarse_points_k(SparseBox b, SparseDims d, uint32_t first, uint32_t count, float* __restrict__ pts) {
+    const uint32_t t = blockIdx.x * SPARSE_BLOCK + threadIdx.x;
+    if (t >= count) return;
+    const uint32_t i = first + t, c = (uint32_t)d.coarse;
+    const uint32_t xy = i / c, kz = i - xy * c, ix = xy / c, jy = xy - ix * c;
+    const int last = d.res - 1;
+    float* p = pts + (size_t)3 * t;
+    p[0] = linspace_at(b.lo[0], b.hi[0], d.res, (int)min(ix * (uint32_t)d.brick, (uint32_t)last));
+    p[1] = linspace_at(b.lo[1], b.hi[1], d.res, (int)min(jy * (uint32_t)d.brick, (uint32_t)last));
+    p[2] = linspace_at(b.lo[2], b.hi[2], d.res, (int)min(kz * (uint32_t)d.brick, (uint32_t)last));
+}
+
+__global__ __launch_bounds__(SPARSE_BLOCK) void classify_k(const float* __restrict__ uc, int c, float t, float margin, uint32_t n,
+                                                           uint8_t* __restrict__ flags) {
+    const uint32_t i = blockIdx.x * SPARSE_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t nb = (uint32_t)c - 1u;
+    const uint32_t xy = i / nb, bz = i - xy * nb, bx = xy / nb, by = xy - bx * nb;
+    bool near = false, any_below = false, all_below = true;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float v = uc[((bx + (k >> 2)) * c + by + ((k >> 1) & 1)) * c + bz + (k & 1)];
+        near = near || !isfinite(v) || fabsf(v - t) <= margin;
+        const bool below = v < t;                     // (a NaN is not below; it made the brick active already)
+        any_below = any_below || below;
+        all_below = all_below && below;
+    }
+    flags[i] = (near || (any_below && !all_below)) ? 1 : 0;
+}
+
+// Row t of a range of listed point bricks -> its UNCLAMPED fine indices; false if the list entry is no point brick (the row is skipped).
+__device__ __forceinline__ bool brick_row(const SparseDims& d, const int64_t* __restrict__ list, uint32_t first, uint32_t t, int& fx, int& fy, int& fz) {
+    const uint32_t b = (uint32_t)d.brick, b3 = b * b * b, p = (uint32_t)d.pbricks;
+    const uint32_t k = t / b3, l = t - k * b3;
+    const int64_t entry = list[first + k];
+    if (entry < 0 || entry >= (int64_t)p * p * p) return false;
+    const uint32_t e = (uint32_t)entry;
+    const uint32_t exy = e / p, ez = e - exy * p, ex = exy / p, ey = exy - ex * p;
+    const uint32_t lxy = l / b, lz = l - lxy * b, lx = lxy / b, ly = lxy - lx * b;
+    fx = (int)(ex * b + lx);
+    fy = (int)(ey * b + ly);
+    fz = (int)(ez * b + lz);
+    return true;
+}
+
+__global__ __launch_bounds__(SPARSE_BLOCK) void brick_points_k(SparseBox bx, SparseDims d, const int64_t* __restrict__ list, uint32_t first, uint32_t rows,
+                                                               float* __restrict__ pts) {
+    const uint32_t t = blockIdx.x * SPARSE_BLOCK + threadIdx.x;
+    if (t >= rows) return;
+    int fx = 0, fy = 0, fz = 0;
+    (void)brick_row(d, list, first, t, fx, fy, fz);         // (a bad entry: the first lattice point, a row the scatter skips too)
+    const int last = d.res - 1;
+    pts[3 * t] = linspace_at(bx.lo[0], bx.hi[0], d.res, min(fx, last));
+    pts[3 * t + 1] = linspace_at(bx.lo[1], bx.hi[1], d.res, min(fy, last));
+    pts[3 * t + 2] = linspace_at(bx.lo[2], bx.hi[2], d.res, min(fz, last));
+}
+
+__global__ __launch_bounds__(SPARSE_BLOCK) void scatter_k(const float* __restrict__ sdf, SparseDims d, const int64_t* __restrict__ list, uint32_t first,
+                                                          uint32_t rows, float* __restrict__ u) {
+    const uint32_t t = blockIdx.x * SPARSE_BLOCK + threadIdx.x;
+    if (t >= rows) return;
+    int fx, fy, fz;
+    if (!brick_row(d, list, first, t, fx, fy, fz)) return;
+    if (fx >= d.res || fy >= d.res || fz >= d.res) return;                                // a clamped duplicate: its owner wrote the value
+    u[((uint32_t)fx * (uint32_t)d.res + (uint32_t)fy) * (uint32_t)d.res + (uint32_t)fz] = -sdf[t];
+}
+
+// the deciding brick's coordinate of fine index i
+__device__ __forceinline__ uint32_t deciding_brick(uint32_t i, uint32_t brick, uint32_t last_brick) { return min(i / brick, last_brick); }
+
+__global__ __launch_bounds__(SPARSE_BLOCK) void fill_k(const float* __restrict__ uc, SparseDims d, uint32_t n, float* __restrict__ u) {
+    const uint32_t q = blockIdx.x * SPARSE_BLOCK + threadIdx.x, i0 = q * 4u;
+    if (i0 >= n) return;
+    const uint32_t r = (uint32_t)d.res, b = (uint32_t)d.brick, c = (uint32_t)d.coarse, lb = c - 2u;
+    const uint32_t xy = i0 / r;
+    uint32_t kz = i0 - xy * r, ix = xy / r, jy = xy - ix * r;
+    uint32_t row = (deciding_brick(ix, b, lb) * c + deciding_brick(jy, b, lb)) * c;
+    float v[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        v[e] = uc[row + deciding_brick(kz, b, lb)];
+        if (++kz == r) {                                   // the next lattice row (past the last point: never stored)
+            kz = 0;
+            if (++jy == r) { jy = 0; ++ix; }
+            row = (deciding_brick(min(ix, r - 1u), b, lb) * c + deciding_brick(jy, b, lb)) * c;
+        }
+    }
+    if (i0 + 4u <= n) {
+        *reinterpret_cast<float4*>(u + i0) = make_float4(v[0], v[1], v[2], v[3]);
+    } else {
+        for (uint32_t e = 0; i0 + e < n; ++e) u[i0 + e] = v[e];
+    }
+}
+
+__global__ __launch_bounds__(SPARSE_BLOCK) void leaks_k(const float* __restrict__ u, SparseDims d, const uint8_t* __restrict__ flags, float t, uint32_t n,
+                                                        unsigned long long* __restrict__ leaks) {
+    const uint32_t i = blockIdx.x * SPARSE_BLOCK + threadIdx.x;
+    uint32_t mine = 0;
+    if (i < n) {
+        const uint32_t r = (uint32_t)d.res, b = (uint32_t)d.brick, nb = (uint32_t)d.coarse - 1u, lb = nb - 1u;
+        const uint32_t xy = i / r, kz = i - xy * r, ix = xy / r, jy = xy - ix * r;
+        const bool below = u[i] < t;
+        const uint32_t step[3] = {r * r, r, 1u}, at[3] = {ix, jy, kz};
+        bool own_known = false, own_active = false;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            if (at[a] + 1u >= r) continue;
+            if ((u[i + step[a]] < t) == below) continue;
+            if (!own_known) {                              // crossing edges are rare: the flags are read for those only
+                own_active = flags[(deciding_brick(ix, b, lb) * nb + deciding_brick(jy, b, lb)) * nb + deciding_brick(kz, b, lb)] != 0;
+                own_known = true;
+            }
+            const uint32_t qx = ix + (a == 0), qy = jy + (a == 1), qz = kz + (a == 2);
+            const bool other_active = flags[(deciding_brick(qx, b, lb) * nb + deciding_brick(qy, b, lb)) * nb + deciding_brick(qz, b, lb)] != 0;
+            if (!own_active || !other_active) ++mine;
+        }
+    }
+    // one atomic per wave that found something: a thread counts 0 to 3 edges: one ballot per bit of that
+    const unsigned long long b0 = __ballot(mine & 1u), b1 = __ballot(mine & 2u);
+    if ((threadIdx.x & 63) == 0 && (b0 | b1)) atomicAdd(leaks, (unsigned long long)(__popcll(b0) + 2 * __popcll(b1)));
+}
+
+extern "C" int gens_sparse_coarse_points(const float* bmin3_host, const float* bmax3_host, int res, int brick, int64_t first, int64_t count,
+                                         float* pts, void* stream) {
+    const char* who = "gens_sparse_coarse_points";
+    if (int e = sparse_check(who, res, brick)) return e;
+    SparseBox b;
+    if (int e = sparse_box(who, bmin3_host, bmax3_host, b)) return e;
+    const SparseDims d = sparse_dims(res, brick);
+    GENS_CHECK_ARG(first >= 0 && count >= 0 && first + count <= (int64_t)d.coarse * d.coarse * d.coarse, GENS_EINVAL,
+                   "%s: range [%lld, %lld) beyond the %d^3 coarse points", who, (long long)first, (long long)(first + count), d.coarse);
+    if (count == 0) return 0;
+    GENS_CHECK_ARG(pts, GENS_EINVAL, "%s: null pointer (pts)", who);
+    coarse_points_k<<<gens_blocks(count, SPARSE_BLOCK), SPARSE_BLOCK, 0, (hipStream_t)stream>>>(b, d, (uint32_t)first, (uint32_t)count, pts);
+    return gens_launch_status(who);
+}
+
+extern "C" int gens_sparse_classify(const float* uc, int res, int brick, float t, float margin, uint8_t* flags, void* stream) {
+    const char* who = "gens_sparse_classify";
+    if (int e = sparse_check(who, res, brick)) return e;
+    GENS_CHECK_ARG(uc && flags, GENS_EINVAL, "%s: null pointer", who);
+    GENS_CHECK_ARG(margin >= 0.0f, GENS_EINVAL, "%s: margin = %g, must be >= 0 (and no NaN)", who, (double)margin);
+    const SparseDims d = sparse_dims(res, brick);
+    const int64_t n = (int64_t)(d.coarse - 1) * (d.coarse - 1) * (d.coarse - 1);
+    classify_k<<<gens_blocks(n, SPARSE_BLOCK), SPARSE_BLOCK, 0, (hipStream_t)stream>>>(uc, d.coarse, t, margin, (uint32_t)n, flags);
+    return gens_launch_status(who);
+}
+
+// The list range of the two per-brick entry points -> rows (brick^3 per entry), or an error code.
+static int sparse_rows(const char* who, const SparseDims& d, const int64_t* list, int64_t n_list, int64_t first, int64_t count, int64_t& rows) {
+    GENS_CHECK_ARG(n_list >= 0 && first >= 0 && count >= 0 && first + count <= n_list, GENS_EINVAL, "%s: range [%lld, %lld) beyond the list of %lld bricks",
+                   who, (long long)first, (long long)(first + count), (long long)n_list);
+    GENS_CHECK_ARG(d.brick <= 1024 && count < ((int64_t)1 << 31), GENS_ELIMIT, "%s: brick = %d (at most 1024), %lld bricks (fewer than 2^31)", who, d.brick,
+                   (long long)count);
+    rows = count * d.brick * d.brick * d.brick;
+    GENS_CHECK_ARG(first < ((int64_t)1 << 31) && rows < ((int64_t)1 << 31) / 3, GENS_ELIMIT, "%s: %lld bricks of %d^3 points: fewer than 2^31 / 3 rows per call",
+                   who, (long long)count, d.brick);
+    GENS_CHECK_ARG(count == 0 || list, GENS_EINVAL, "%s: null pointer (list)", who);
+    return 0;
+}
+
+extern "C" int gens_sparse_brick_points(const float* bmin3_host, const float* bmax3_host, int res, int brick, const int64_t* list, int64_t n_list,
+                                        int64_t first, int64_t count, float* pts, void* stream) {
+    const char* who = "gens_sparse_brick_points";
+    if (int e = sparse_check(who, res, brick)) return e;
+    SparseBox b;
+    if (int e = sparse_box(who, bmin3_host, bmax3_host, b)) return e;
+    const SparseDims d = sparse_dims(res, brick);
+    int64_t rows = 0;
+    if (int e = sparse_rows(who, d, list, n_list, first, count, rows)) return e;
+    if (rows == 0) return 0;
+    GENS_CHECK_ARG(pts, GENS_EINVAL, "%s: null pointer (pts)", who);
+    brick_points_k<<<gens_blocks(rows, SPARSE_BLOCK), SPARSE_BLOCK, 0, (hipStream_t)stream>>>(b, d, list, (uint32_t)first, (uint32_t)rows, pts);
+    return gens_launch_status(who);
+}
+
+extern "C" int gens_sparse_fill(const float* uc, int res, int brick, float* u, void* stream) {
+    const char* who = "gens_sparse_fill";
+    if (int e = sparse_check(who, res, brick)) return e;
+    GENS_CHECK_ARG(uc && u, GENS_EINVAL, "%s: null pointer", who);
+    GENS_CHECK_ARG(((uintptr_t)u & 15) == 0 && ((uintptr_t)uc & 3) == 0, GENS_EINVAL, "%s: misaligned pointer (u: 16 bytes; uc: 4 bytes)", who);
+    const SparseDims d = sparse_dims(res, brick);
+    const int64_t n = (int64_t)res * res * res;
+    fill_k<<<gens_blocks((n + 3) / 4, SPARSE_BLOCK), SPARSE_BLOCK, 0, (hipStream_t)stream>>>(uc, d, (uint32_t)n, u);
+    return gens_launch_status(who);
+}
+
+extern "C" int gens_sparse_scatter(const float* sdf, int res, int brick, const int64_t* list, int64_t n_list, int64_t first, int64_t count, float* u,
+                                   void* stream) {
+    const char* who = "gens_sparse_scatter";
+    if (int e = sparse_check(who, res, brick)) return e;
+    const SparseDims d = sparse_dims(res, brick);
+    int64_t rows = 0;
+    if (int e = sparse_rows(who, d, list, n_list, first, count, rows)) return e;
+    if (rows == 0) return 0;
+    GENS_CHECK_ARG(sdf && u, GENS_EINVAL, "%s: null pointer", who);
+    scatter_k<<<gens_blocks(rows, SPARSE_BLOCK), SPARSE_BLOCK, 0, (hipStream_t)stream>>>(sdf, d, list, (uint32_t)first, (uint32_t)rows, u);
+    return gens_launch_status(who);
+}
+
+extern "C" int gens_sparse_leaks(const float* u, int res, int brick, const uint8_t* flags, float t, int64_t* leaks, void* stream) {
+    const char* who = "gens_sparse_leaks";
+    if (int e = sparse_check(who, res, brick)) return e;
+    GENS_CHECK_ARG(u && flags && leaks, GENS_EINVAL, "%s: null pointer", who);
+    GENS_CHECK_ARG(((uintptr_t)leaks & 7) == 0 && ((uintptr_t)u & 3) == 0, GENS_EINVAL, "%s: misaligned pointer (u: 4 bytes; leaks: 8 bytes)", who);
+    const SparseDims d = sparse_dims(res, brick);
+    const int64_t n = (int64_t)res * res * res;
+    hipStream_t s = (hipStream_t)stream;
+    if (hipError_t e = hipMemsetAsync(leaks, 0, sizeof(int64_t), s)) {
+        (void)hipGetLastError();
+        gens_set_error("%s: clearing the count: %s", who, hipGetErrorString(e));
+        return (int)e;
+    }
+    leaks_k<<<gens_blocks(n, SPARSE_BLOCK), SPARSE_BLOCK, 0, s>>>(u, d, flags, t, (uint32_t)n, (unsigned long long*)leaks);
+    return gens_launch_status(who);
+}

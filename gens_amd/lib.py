@@ -194,6 +194,12 @@ SIGNATURES = {
     "gens_components_scratch_bytes": [_i, _i, _i],          # (returns int64 bytes, not a status: load() sets its restype; call it through lib)
     "gens_largest_component": [_p, _i, _i, _i, _i, _p, _p, _p, _p],
     "gens_unpack_mask_bits": [_p, _l, _p, _p],
+    "gens_sparse_coarse_points": [_fp, _fp, _i, _i, _l, _l, _p, _p],
+    "gens_sparse_classify": [_p, _i, _i, _f, _f, _p, _p],
+    "gens_sparse_brick_points": [_fp, _fp, _i, _i, _p, _l, _l, _l, _p, _p],
+    "gens_sparse_fill": [_p, _i, _i, _p, _p],
+    "gens_sparse_scatter": [_p, _i, _i, _p, _l, _l, _l, _p, _p],
+    "gens_sparse_leaks": [_p, _i, _i, _p, _f, _p, _p],
 }
 
 _lib = None

@@ -91,6 +91,12 @@ class GenS(nn.Module):
         keep = confs.get("filter_keep_largest", None)           # optional: filter_volume keeps only the band's largest region (clean_volume)
         if keep is not None:
             self.filter_keep_largest = bool(keep)
+        brick = confs.get("sparse_lattice", None)               # optional: extract_geometry's two-level lattice (a brick edge, or True)
+        if brick is not None:
+            self.implicit_surface.sparse_lattice = brick if isinstance(brick, bool) else int(brick)
+        lipschitz = confs.get("lattice_lipschitz", None)        # optional: the bound that lattice assumes (ImplicitSurface.lattice_lipschitz)
+        if lipschitz is not None:
+            self.implicit_surface.lattice_lipschitz = float(lipschitz)
 
     # -- optimiser / checkpoint plumbing (gens.py:32-61) --------------------------------------------------------
     def get_optim_params(self, lr_confs):

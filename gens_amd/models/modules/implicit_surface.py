@@ -568,29 +568,66 @@ class ImplicitSurface(nn.Module):
     # ----------------------------------------------------------------------------------------------------------
     # geometry + validation
     # ----------------------------------------------------------------------------------------------------------
+    sparse_lattice = None          # brick edge of the two-level lattice (ops.sparse_lattice, K28); None: the dense lattice, True: SPARSE_BRICK
+    lattice_lipschitz = 2.0        # assumed bound on |d sdf| per unit length between lattice points: twice the eikonal target.  A heuristic;
+                                   # the leak count of every sparse call checks it and falls back to the dense lattice when it fails
+    last_lattice_stats = None      # ops.sparse_lattice's stats of the last sdf_grid call (None: that call was dense)
+    SPARSE_BRICK = 4               # what `sparse=True` means: the brick edge that measured best at 512^3 and 1024^3
+
+    def _lattice_brick(self, sparse, shard):
+        """The brick edge of this call, or None for the dense lattice.  sparse: None = the attribute `sparse_lattice`, False = dense."""
+        if sparse is None:
+            sparse = self.sparse_lattice
+        if sparse is None or sparse is False:
+            return None
+        brick = self.SPARSE_BRICK if sparse is True else int(sparse)
+        if brick < 1:
+            raise ValueError(f"sparse = {sparse!r}: the brick edge in cells, at least 1 (or True / None)")
+        if shard is not None:
+            if not getattr(self, "_warned_sparse_shard", False):
+                import warnings
+                warnings.warn("gens_amd: the sparse lattice is not sharded: with a shard the dense lattice is evaluated", RuntimeWarning, stacklevel=3)
+                self._warned_sparse_shard = True
+            return None
+        return brick
+
     @torch.no_grad()
-    def sdf_grid(self, volumes, bound_min, bound_max, resolution, chunk=1 << 21, shard=None):
+    def sdf_grid(self, volumes, bound_min, bound_max, resolution, chunk=1 << 21, shard=None, sparse=None, threshold=0.0):
         """u = -sdf on the resolution^3 lattice (:407-421), kept on the device.  shard (gens_amd.distributed.Shard): this rank evaluates
-        the chunks `index mod world` and the slabs are gathered on every rank (None under Shard.single until the last shard arrives)."""
+        the chunks `index mod world` and the slabs are gathered on every rank (None under Shard.single until the last shard arrives).
+        sparse (a brick edge in cells, True for SPARSE_BRICK; default: the attribute `sparse_lattice`, None = off): the network is evaluated
+        on every sparse-th point and inside the bricks that can hold the surface u = threshold, under the bound `lattice_lipschitz`
+        (ops.sparse_lattice); marching cubes at `threshold` then returns the dense lattice's mesh.  Ignored with a shard."""
         vols = volumes if isinstance(volumes, ops.VolumeSet) else ops.VolumeSet.packed(volumes)
         dev = vols.tensors[0].device
         total = resolution ** 3
         n_chunks = -(-total // chunk)
         own = range(n_chunks) if shard is None else shard.chunks(n_chunks)
-        u = torch.zeros(len(own), chunk, device=dev) if shard is not None else torch.empty(total, device=dev)
+        brick = self._lattice_brick(sparse, shard)
+        self.last_lattice_stats = None
+        if brick is None:
+            u = torch.zeros(len(own), chunk, device=dev) if shard is not None else torch.empty(total, device=dev)
         split_half = None                              # a value outside the half range: the lattice again in float32, like the image
         for attempt in range(2):
-            for k, c in enumerate(own):
-                first = c * chunk
-                count = min(chunk, total - first)
-                pts = ops.lattice_points(bound_min.tolist(), bound_max.tolist(), resolution, first, count, dev)
+            def evaluate(pts):
                 plan = self._fused_plan(vols)
                 prec = "f32" if split_half is False else self._precision(plan) if plan is not None else "f32"
-                sdf = ops.sdf_mlp(plan, vols, pts, precision=prec) if plan is not None else self.sdf_network.sdf(pts, vols)
-                if shard is not None:
-                    u[k, :count] = -sdf[:, 0]
-                else:
-                    u[first:first + count] = -sdf[:, 0]
+                return ops.sdf_mlp(plan, vols, pts, precision=prec) if plan is not None else self.sdf_network.sdf(pts, vols)
+
+            if brick is not None:                      # coarse and fine passes together; an overflow repeats both
+                u, self.last_lattice_stats = ops.sparse_lattice(evaluate, bound_min.tolist(), bound_max.tolist(), resolution, threshold, brick,
+                                                                self.lattice_lipschitz, chunk=chunk, device=dev)
+                u = u.reshape(-1)
+            else:
+                for k, c in enumerate(own):
+                    first = c * chunk
+                    count = min(chunk, total - first)
+                    pts = ops.lattice_points(bound_min.tolist(), bound_max.tolist(), resolution, first, count, dev)
+                    sdf = evaluate(pts)
+                    if shard is not None:
+                        u[k, :count] = -sdf[:, 0]
+                    else:
+                        u[first:first + count] = -sdf[:, 0]
             overflowed = split_half is not False and self._split_half_overflowed()
             if shard is not None and split_half is not False and self.sdf_precision == "f16x2":
                 overflowed = shard.any(overflowed)
@@ -604,10 +641,11 @@ class ImplicitSurface(nn.Module):
             u = u.reshape(-1)[:total]
         return u.reshape(resolution, resolution, resolution)
 
-    def extract_geometry(self, volumes, bound_min, bound_max, resolution, threshold, shard=None):
+    def extract_geometry(self, volumes, bound_min, bound_max, resolution, threshold, shard=None, sparse=None):
         """-> vertices (V,3) float64, triangles (T,3) int32 as numpy arrays (implicit_surface.py:407-427).  The SDF lattice and
-        the marching cubes both run on the device (the reference: 512 D2H copies + PyMCubes on the host); only the mesh is copied."""
-        u = self.sdf_grid(volumes, bound_min, bound_max, resolution, shard=shard)
+        the marching cubes both run on the device (the reference: 512 D2H copies + PyMCubes on the host); only the mesh is copied.
+        sparse: sdf_grid's option of that name, with this call's threshold."""
+        u = self.sdf_grid(volumes, bound_min, bound_max, resolution, shard=shard, sparse=sparse, threshold=threshold)
         if u is None:
             return None, None
         vertices, triangles = ops.marching_cubes(u, threshold)
@@ -618,11 +656,11 @@ class ImplicitSurface(nn.Module):
 
     @torch.no_grad()
     def validate(self, rays_o, rays_d, near, far, volumes, mask_volumes, imgs, features, match_features, intrs, c2ws, bound_min, bound_max,
-                 hw, cos_anneal_ratio=1.0, step=None, extract_geometry=True, mesh_resolution=512, threshold=0.0, scene=None, shard=None):
+                 hw, cos_anneal_ratio=1.0, step=None, extract_geometry=True, mesh_resolution=512, threshold=0.0, scene=None, shard=None, sparse=None):
         """shard (gens_amd.distributed.Shard, optional): render only this rank's contiguous ray range and evaluate only its lattice
         chunks; the (P, 8) image buffer / the lattice slabs are gathered over RCCL, so every rank returns the whole image.  The jitter
         of EVERY ray is drawn on every rank from the identically seeded CPU generator (the reference's draw order) and sliced with
-        the rays: the image does not depend on the partition."""
+        the rays: the image does not depend on the partition.  sparse: extract_geometry's option (the two-level lattice)."""
         outputs = {}
         if scene is None:
             scene = Scene(volumes, mask_volumes, imgs, features, match_features, intrs, c2ws)
@@ -642,7 +680,7 @@ class ImplicitSurface(nn.Module):
             import time
             t_geo = time.perf_counter()
             outputs["vertices"], outputs["triangles"] = self.extract_geometry(scene.volumes_nograd(), bound_min, bound_max, mesh_resolution,
-                                                                              threshold, shard=shard)
+                                                                              threshold, shard=shard, sparse=sparse)
             self.last_geometry_s = time.perf_counter() - t_geo     # (ends with the mesh's read-back: wall time is the item's share; bench.py's default_path)
         # one (P, 8) device buffer [rgb | normal | sdf_depth | render_depth] filled chunk by chunk: ONE D2H copy per image
         # into a pinned host buffer (the reference copies 4 tensors per 256-ray chunk, implicit_surface.py:446-453)

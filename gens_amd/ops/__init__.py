@@ -21,6 +21,7 @@ is what it was when ops was one module:
     ops.finalize  K25: elliptical dilation and vertex mask votes of the DTU mesh finalising (evaluation/clean_meshes.py).
     ops.filter    K26: the mask pyramid restricted to the dilated SDF band (GenS.filter_volume, models/gens.py:87-122);
                   K27: the largest connected region of a mask volume (clean_volume, utils/tools.py:34-50).
+    ops.lattice   K28: the two-level SDF lattice of extract_geometry, evaluated near the iso-surface only (sparse_lattice).
 """
 from .base import *  # noqa: F401,F403
 from .volume import *  # noqa: F401,F403
@@ -35,3 +36,4 @@ from .conv2d import *  # noqa: F401,F403
 from .points import *  # noqa: F401,F403
 from .finalize import *  # noqa: F401,F403
 from .filter import *  # noqa: F401,F403
+from .lattice import *  # noqa: F401,F403

@@ -59,7 +59,8 @@ const char* gens_last_error(void);
  *       gens_mesh_grid_{count,fill}, gens_ray_first_hit, gens_view_rays_hit_faces, gens_face_cc_{hook,compress}, and K24's
  *       gens_mesh_sample_{count,emit}, gens_point_grid_{count,fill}, gens_radius_downsample_round, gens_nearest_point, and K25's
  *       gens_dilate_u8, gens_vertex_mask_votes, gens_view_rays_hit_counts, and K26's gens_filter_masks, gens_filter_band, gens_filter_levels,
- *       and K27's gens_largest_component, gens_components_scratch_bytes, gens_unpack_mask_bits. */
+ *       and K27's gens_largest_component, gens_components_scratch_bytes, gens_unpack_mask_bits, and K28's gens_sparse_coarse_points,
+ *       gens_sparse_classify, gens_sparse_brick_points, gens_sparse_fill, gens_sparse_scatter, gens_sparse_leaks. */
 int gens_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -819,6 +820,39 @@ int64_t gens_components_scratch_bytes(int nx, int ny, int nz);
 int gens_largest_component(const uint32_t* bits_in, int nx, int ny, int nz, int connectivity, uint32_t* bits_out, void* scratch,
                            int64_t* results, void* stream);
 int gens_unpack_mask_bits(const uint32_t* bits, int64_t n, float* mask, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * K28  The two-level lattice of extract_geometry (implicit_surface.py:407-427): the network is evaluated on every brick-th lattice point
+ *      and inside the bricks that can contain the iso-surface; six streaming launches around the caller's evaluator (ops.sparse_lattice).
+ *   res = R >= 2 lattice points per axis with R^3 < 2^31 (GENS_ELIMIT beyond: all point indices are 32-bit); brick = B >= 1 cells.
+ *   C = ceil((R - 1) / B) + 1 coarse points per axis, coarse index i = fine index min(i * B, R - 1); (C - 1)^3 bricks in C order
+ *   [bx, by, bz], brick b between the coarse points b and b + 1 of each axis.  The brick that DECIDES for fine index i is min(i / B, C - 2).
+ *   Point bricks: fine index i is OWNED by point brick i / B of P = ceil(R / B) per axis (P == C - 1 unless (R - 1) % B == 0: then the
+ *   plane R - 1 is a point brick of its own, decided by the brick below it).  A list entry is a point brick's C-order number in the P^3
+ *   grid and stands for B^3 rows in brick-local C order [lx, ly, lz], fine index e * B + l per axis.
+ *   Coordinates: gens_lattice_points' formula at the fine index, bit for bit.  bmin3_host / bmax3_host: three HOST floats each.
+ *     gens_sparse_coarse_points: pts (count, 3) = the coarse points first .. first + count - 1 in C order of the C^3 grid.
+ *     gens_sparse_classify: uc (C^3) = u at the coarse points -> flags ((C - 1)^3) bytes: 1 if a corner of the brick is non-finite, or
+ *       has |u - t| <= margin (float32; margin >= 0), or the 8 corners disagree on u < t; else 0.
+ *     gens_sparse_brick_points: pts (count * B^3, 3) for the entries list[first .. first + count); an index past R - 1 is clamped to it.
+ *     gens_sparse_fill: u (R^3, 16-byte aligned) <- for every fine point the value of uc at its deciding brick's lowest corner.
+ *     gens_sparse_scatter: sdf (count * B^3) in gens_sparse_brick_points' row order -> u[fine point] = -sdf[row] for the rows whose
+ *       indices are all <= R - 1 (the others are the clamped duplicates).  An entry outside the P^3 grid is skipped.
+ *     gens_sparse_leaks: leaks (one device int64, 8-byte aligned, SET by the call) = the number of lattice edges (p, p + e_axis) with
+ *       (u[p] < t) != (u[q] < t) and flags == 0 at the deciding brick of p or of q.
+ *   list: n_list int64 on the DEVICE (gens_compact_valid's output); first >= 0, count >= 0, first + count <= n_list (GENS_EINVAL);
+ *   B <= 1024 and count * B^3 < 2^31 / 3 rows per call (GENS_ELIMIT).  Every pointer non-null (a zero count needs none).  Arguments are
+ *   checked before any launch.
+ * ---------------------------------------------------------------------------------------------------------- */
+int gens_sparse_coarse_points(const float* bmin3_host, const float* bmax3_host, int res, int brick, int64_t first, int64_t count, float* pts,
+                              void* stream);
+int gens_sparse_classify(const float* uc, int res, int brick, float t, float margin, uint8_t* flags, void* stream);
+int gens_sparse_brick_points(const float* bmin3_host, const float* bmax3_host, int res, int brick, const int64_t* list, int64_t n_list,
+                             int64_t first, int64_t count, float* pts, void* stream);
+int gens_sparse_fill(const float* uc, int res, int brick, float* u, void* stream);
+int gens_sparse_scatter(const float* sdf, int res, int brick, const int64_t* list, int64_t n_list, int64_t first, int64_t count, float* u,
+                        void* stream);
+int gens_sparse_leaks(const float* u, int res, int brick, const uint8_t* flags, float t, int64_t* leaks, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K14  C (m x n) = A^T B for tall row-major operands A (k x m), B (k x n), k >> m, n: the weight-gradient product of the training
