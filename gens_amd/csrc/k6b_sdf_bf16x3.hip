@@ -18,17 +18,14 @@
 //   * softplus and softplus' (float32), the trilinear look-up and its Jacobians, the stash of layer 2's softplus' and the chain rule to x
 //     are k6gh's; the gradients need no scaling (bf16 has float32's range).
 #include "common.h"
+#include "split3.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
 typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 #define GB_WAVES 4
 #define GB_PIECE 1024                       // bytes of one piece: 64 lanes x 8 bf16
-#define GB_TERMS 3                          // pieces per (K block, output tile): x0, x1, x2
+#define GB_TERMS SPLIT3_TERMS               // pieces per (K block, output tile): x0, x1, x2 (split3.h)
 #define GB_CH 8                             // pieces per chunk of the ring
 #define GB_RING 4
 #define GB_GT 2                             // output tiles per group of A operands
@@ -42,30 +39,6 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 #define GB_SLOTS 2048                       // (XCC 3 bits, SE 2, CU 4, wave 2)
 #define GB_C 144.26950408889634f            // 100 / ln 2: hidden units travel as c * softplus (k6_sdfmlp.hip::softplus_t)
 
-struct Split3Block {      // the B operand of one 16-deep K block: this lane's 8 values as three bf16 terms
-    u32x4 p[GB_TERMS];
-};
-
-struct Split3Word {
-    uint32_t w[GB_TERMS];
-};
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {      // v_cvt_pk_bf16_f32: a -> bits [15:0], b -> [31:16], nearest even
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2v){a, b}, bf16x2));
-}
-// (a, b) -> their three packed terms; the residuals a - x0, a - x0 - x1 are exact in float32
-__device__ __forceinline__ Split3Word split3_pair(float a, float b) {
-    Split3Word s;
-#pragma unroll
-    for (int k = 0; k < GB_TERMS; ++k) {
-        const uint32_t w = pk_bf16(a, b);
-        s.w[k] = w;
-        if (k + 1 < GB_TERMS) {
-            a -= __builtin_bit_cast(float, w << 16);
-            b -= __builtin_bit_cast(float, w & 0xffff0000u);
-        }
-    }
-    return s;
-}
 #define GB_PUT(BLK_, W_, A_, B_)                                            \
     {                                                                       \
         const Split3Word sw__ = split3_pair((A_), (B_));                    \

@@ -21,7 +21,8 @@ class KernelChoice:
     attributes; nothing on a launch path reads os.environ.
         sdf_value / sdf_grad   "bf16x3" (k6b: three-term bfloat16 operands, float32-accurate; the default, 3 and 5 levels -- other level counts
                                take "transposed") | "transposed" (k6t / k6g: float32 MFMA, register-chained) | "rowmajor" (k6_sdfmlp.hip: cross-check)
-        blend                  "transposed" (k7t, two to four source views) | "rowmajor" (k7_blend.hip)
+        blend                  "bf16x3" (k7b: k7t with three-term bfloat16 operands, float32-accurate; the default, two to four source views) |
+                               "transposed" (k7t: float32 MFMA) | "rowmajor" (k7_blend.hip; always for other view counts)
         blend_train_fwd        "transposed" (the training step's forward through k7t + gens_blend_pack_t) | "rowmajor" (k18's own forward)
         blend_train_wgrad      "inside" (the weight-gradient sums inside the backward launch, gens_blend_train_bwd_acc) | "rows" (operand rows + K14)
         blend_train_bwd        "transposed" (two to four source views: gens_blend_train_bwd_t, a wave per 16 rows, weights in LDS) | "rowmajor" (k18's
@@ -37,7 +38,7 @@ class KernelChoice:
         self.sdf_value = "rowmajor" if env.get("GENS_SDF_VALUE_ROWMAJOR") else f32_mfma
         self.sdf_grad = "rowmajor" if env.get("GENS_SDF_GRAD_ROWMAJOR") else f32_mfma
         self.sdf_grad_f16 = not env.get("GENS_SDF_GRAD_F32_ONLY")
-        self.blend = "rowmajor" if env.get("GENS_BLEND_ROWMAJOR") else "transposed"
+        self.blend = "rowmajor" if env.get("GENS_BLEND_ROWMAJOR") else "transposed" if env.get("GENS_BLEND_F32_MFMA") else "bf16x3"
         self.blend_train_fwd = "rowmajor" if env.get("GENS_BLEND_TRAIN_ROWMAJOR") else "transposed"
         self.blend_train_wgrad = "rows" if env.get("GENS_K18_OPERAND_ROWS") else "inside"
         self.blend_train_bwd = "rowmajor" if env.get("GENS_BLEND_TRAIN_BWD_ROWMAJOR") or env.get("GENS_K18_OPERAND_ROWS") else "transposed"

@@ -13,6 +13,53 @@ def _pad32(b):
     return out
 
 
+def _blend_fragments(w, slots, m_tiles, bias=None, quads=4):
+    """A fragments of one product of the transposed blending kernels, in consumption order (M tile outer, K group inner): per (M tile T,
+    group g of `quads` K quads) a (64, quads) float32 array that holds for lane (m, qk) and j = 0 .. quads - 1 the weight
+    W[16 T + 4 (m & 3) + (m >> 2)][slot 4 (quads g + j) + qk].  w (O, I); slots: list of source columns per input slot (-1: the bias,
+    -2: nothing), padded to whole groups with zeros."""
+    dev = w.device
+    lane = torch.arange(64, device=dev)
+    m, qk = lane & 15, lane >> 4
+    row_in_tile = 4 * (m & 3) + (m >> 2)
+    o = w.shape[0]
+    aug = torch.cat([w, (bias if bias is not None else torch.zeros(o, device=dev))[:, None], torch.zeros(o, 1, device=dev)], 1)
+    aug = torch.cat([aug, torch.zeros(16 * m_tiles - o, aug.shape[1], device=dev)], 0) if 16 * m_tiles > o else aug
+    cols = torch.tensor([c if c >= 0 else (w.shape[1] if c == -1 else w.shape[1] + 1) for c in slots], device=dev)
+    nq = (len(slots) + 3) // 4
+    cols = torch.cat([cols, torch.full((4 * nq - len(slots),), w.shape[1] + 1, device=dev)])
+    groups = []
+    for t in range(m_tiles):
+        rows = 16 * t + row_in_tile
+        for g in range((nq + quads - 1) // quads):
+            frag = torch.zeros(64, quads, device=dev, dtype=_f32)
+            for j in range(quads):
+                kq = quads * g + j
+                if kq < nq:
+                    frag[:, j] = aug[rows, cols[4 * kq + qk]]
+            groups.append(frag)
+    return groups
+
+
+def _blend_products(layers, n_feat):
+    """The products of the transposed blending kernels in consumption order: name -> (weight, slots, M tiles, bias in a slot or None)."""
+    f = n_feat
+    xq = (f + 1) // 4
+    xt = (xq + 3) // 4
+    pad = [-2] * (4 * xq - f)
+    b1, r1 = layers["b1"], layers["r1"]
+    return dict(rd1=(layers["rd1"][0], [0, 1, 2, 3], 1, None),
+                rd2=(layers["rd2"][0], list(range(16)), xt, None),
+                b1mv=(b1[0], list(range(f)) + pad + list(range(f, 2 * f)) + pad, 4, None),             # mean | var, once per point
+                b1x=(b1[0], list(range(2 * f, 3 * f)) + [-1], 4, b1[1]),                               # x and the bias (slot F)
+                b2=(layers["b2"][0], list(range(64)), 2, None),
+                v1=(layers["v1"][0], list(range(32)), 2, None),
+                v2=(layers["v2"][0][:32], list(range(32)), 2, None),
+                u1=(layers["u1"][0], list(range(32)), 2, None),
+                r1=(r1[0], list(range(36)) + [36, -1, -2, -2], 1, r1[1]),
+                r2=(layers["r2"][0], list(range(16)), 1, None))
+
+
 def _pack_blend_t(layers, n_feat):
     """Weight stream and tables of gens_blend_views_t (k7t_blend.hip).  Activations live in "quad layout" (feature f = 4 kq + q: register
     kq of lane group q); an A fragment of (M tile T, group g of four K quads) holds for lane (m, qk) and j = 0..3 the weight
@@ -21,44 +68,11 @@ def _pack_blend_t(layers, n_feat):
     f = n_feat
     xq = (f + 1) // 4
     dev = layers["rd1"][0].device
-    lane = torch.arange(64, device=dev)
-    m, qk = lane & 15, lane >> 4
-    row_in_tile = 4 * (m & 3) + (m >> 2)
-
-    def product(w, slots, m_tiles, bias=None):
-        """w (O, I); slots: list of source columns per input slot (-1: the bias, -2: nothing), padded to whole quads."""
-        o = w.shape[0]
-        aug = torch.cat([w, (bias if bias is not None else torch.zeros(o, device=dev))[:, None], torch.zeros(o, 1, device=dev)], 1)
-        aug = torch.cat([aug, torch.zeros(16 * m_tiles - o, aug.shape[1], device=dev)], 0) if 16 * m_tiles > o else aug
-        cols = torch.tensor([c if c >= 0 else (w.shape[1] if c == -1 else w.shape[1] + 1) for c in slots], device=dev)
-        nq = (len(slots) + 3) // 4
-        cols = torch.cat([cols, torch.full((4 * nq - len(slots),), w.shape[1] + 1, device=dev)])
-        groups = []
-        for t in range(m_tiles):
-            rows = 16 * t + row_in_tile
-            for g in range((nq + 3) // 4):
-                frag = torch.zeros(64, 4, device=dev, dtype=_f32)
-                for j in range(4):
-                    kq = 4 * g + j
-                    if kq < nq:
-                        frag[:, j] = aug[rows, cols[4 * kq + qk]]
-                groups.append(frag)
-        return groups
-
-    rd1, rd2, b1, b2, v1, v2, u1, u2, r1, r2, r3 = (layers[k] for k in ("rd1", "rd2", "b1", "b2", "v1", "v2", "u1", "u2", "r1", "r2", "r3"))
+    rd1, rd2, b2, v1, v2, u1, u2, r2, r3 = (layers[k] for k in ("rd1", "rd2", "b2", "v1", "v2", "u1", "u2", "r2", "r3"))
     xt = (xq + 3) // 4
     g = []
-    g += product(rd1[0], [0, 1, 2, 3], 1)
-    g += product(rd2[0], list(range(16)), xt)
-    pad = [-2] * (4 * xq - f)
-    g += product(b1[0], list(range(f)) + pad + list(range(f, 2 * f)) + pad, 4)                         # mean | var, once per point
-    g += product(b1[0], list(range(2 * f, 3 * f)) + [-1], 4, b1[1])                                    # x and the bias (slot F)
-    g += product(b2[0], list(range(64)), 2)
-    g += product(v1[0], list(range(32)), 2)
-    g += product(v2[0][:32], list(range(32)), 2)
-    g += product(u1[0], list(range(32)), 2)
-    g += product(r1[0], list(range(36)) + [36, -1, -2, -2], 1, r1[1])
-    g += product(r2[0], list(range(16)), 1)
+    for w, slots, m_tiles, bias in _blend_products(layers, f).values():
+        g += _blend_fragments(w, slots, m_tiles, bias)
     stream = torch.stack(g + [torch.zeros(64, 4, device=dev, dtype=_f32)] * 2).contiguous()
 
     def acc_bias(b, m_tiles):            # [q][4 T + i] = b[16 T + 4 i + q]
@@ -79,6 +93,40 @@ def _pack_blend_t(layers, n_feat):
     tab = torch.stack([acc_bias(rd1[1], 1), acc_bias(rd2[1], xt), acc_bias(b2[1], 2), acc_bias(v1[1], 2), acc_bias(v2[1][:32], 2),
                        acc_bias(u1[1], 2), acc_bias(r2[1], 1), dot_row(v2[0][32]), dot_row(u2[0][0]), dot_row(r3[0][0])]).contiguous()
     return stream, tab
+
+
+def _split3_planes(x):
+    """float32 (..., 8) -> int32 (3, ..., 4): the three round-to-nearest bfloat16 terms x0 + x1 + x2 = x (the residuals are exact in
+    float32), slot 2 w in the low half of word w, slot 2 w + 1 in the high half."""
+    planes, r = [], x.to(_f32)
+    for k in range(3):
+        t = r.to(torch.bfloat16)
+        planes.append(t.contiguous().view(torch.int32))
+        if k < 2:
+            r = r - t.to(_f32)
+    return torch.stack(planes)
+
+
+def _pack_blend_b(layers, n_feat):
+    """Weight stream of gens_blend_views_bf16x3 (k7b_blend_bf16x3.hip): GROUPS of three 1 KB pieces (64 lanes x 16 bytes) in consumption
+    order.  A bf16 group is the three bfloat16 planes of one (M tile T, K block of eight K quads): lane (m, qk) holds for j = 0..7 the
+    weight W[16 T + 4 (m & 3) + (m >> 2)][slot 4 (8 block + j) + qk] -- _pack_blend_t's quad layout with eight quads per fragment.  The
+    first group is the float32 fragments [ray_dir_fc.0 | ray_dir_fc.2 tile 0 | tile 1] and the last one [rgb_fc.0 quads 8, 9 | rgb_fc.2 | 0]
+    in _pack_blend_t's float4 layout.  Returns the stream (G + 2, 3, 64, 4) int32, the two trailing groups zero; the tables are
+    _pack_blend_t's."""
+    prod = _blend_products(layers, n_feat)
+    dev = layers["rd1"][0].device
+    zero = torch.zeros(64, 4, device=dev, dtype=torch.int32)
+    f32 = lambda name, first=0: [fr.contiguous().view(torch.int32) for fr in _blend_fragments(*prod[name])[first:]]  # noqa: E731
+    bf = lambda name, blocks=None: [_split3_planes(fr) for fr in _blend_fragments(*prod[name], quads=8)[:blocks]]    # noqa: E731
+    head = f32("rd1") + f32("rd2")
+    groups = [torch.stack(head + [zero] * (3 - len(head)))]
+    for name in ("b1mv", "b1x", "b2", "v1", "v2", "u1"):
+        groups += bf(name)
+    groups += bf("r1", 1)                                   # rgb_fc.0: x's 32 columns; quads 8, 9 follow in float32
+    tail = _blend_fragments(*prod["r1"])[2:]                # its third float4 group = quads 8, 9
+    groups.append(torch.stack([tail[0].contiguous().view(torch.int32)] + f32("r2") + [zero]))
+    return torch.stack(groups + [torch.zeros(3, 64, 4, device=dev, dtype=torch.int32)] * 2).contiguous()
 
 
 class BlendPlan:
@@ -110,9 +158,11 @@ class BlendPlan:
                             N(r1[0], [(0, 4), (16, 4), (32, 2)]), _pad32(r1[1]), N(r2[0], [(0, 4)]), _pad32(r2[1]), _c(r3[0][0].clone())]
             self.scalars = (C.c_float * 4)(float(v2[1][32]), float(u2[1][0]), float(r3[1][0]), float(net.s.detach().abs()))
             self.finite = bool(torch.stack([torch.isfinite(p.detach()).all() for p in net.parameters()]).all())
-            self.t_stream, self.t_tab = _pack_blend_t(dict(rd1=rd1, rd2=rd2, b1=b1, b2=b2, v1=v1, v2=v2, u1=u1, u2=u2, r1=r1, r2=r2, r3=r3),
-                                                      self.n_feat)
+            layers = dict(rd1=rd1, rd2=rd2, b1=b1, b2=b2, v1=v1, v2=v2, u1=u1, u2=u2, r1=r1, r2=r2, r3=r3)
+            self.t_stream, self.t_tab = _pack_blend_t(layers, self.n_feat)
             assert self.t_stream.shape[0] == L.load().gens_blend_views_t_groups((self.n_feat - 3) // 4) + 2
+            self.b_stream = _pack_blend_b(layers, self.n_feat)
+            assert self.b_stream.shape[0] == L.load().gens_blend_bf16x3_groups((self.n_feat - 3) // 4) + 2
         self.table = L.ptr_table(self.tensors)
         self.key = BlendPlan.version(net)
 
@@ -134,11 +184,13 @@ def blend_views(plan, views, pts, index=None, rgb_out=None, vis_out=None, count=
     f = plan.n_feat
     flops = 2 * s * (4 * 16 + 16 * f + 3 * f * 64 + 64 * 32 + 32 * 32 + 32 * 33 + 32 * 32 + 32 + 37 * 16 + 16 * 8 + 8)
     nbytes = n * (12 + 12 + s + (8 if idx is not None else 0))
-    if 2 <= s <= 4 and kernels.blend == "transposed":                  # two to four source views: the transposed kernel (k7t_blend.hip)
-        L.call("gens_blend_views_t", L.ptr_table(feats, align=16), L.int_table(hw), nl, L.ptr(aligned16(views.imgs_tex.detach()), align=16),
-               L.ptr(views.w2c), L.ptr(views.intr), L.ptr(views.c2w), views.nv, L.ptr(plan.t_stream), L.ptr(plan.t_tab), plan.scalars, L.ptr(pts),
+    if 2 <= s <= 4 and kernels.blend in ("bf16x3", "transposed"):      # two to four source views: the transposed kernels
+        bf16 = kernels.blend == "bf16x3"          # k7b_blend_bf16x3.hip (three-term bfloat16 operands) | k7t_blend.hip (float32 MFMA)
+        L.call("gens_blend_views_bf16x3" if bf16 else "gens_blend_views_t", L.ptr_table(feats, align=16), L.int_table(hw), nl,
+               L.ptr(aligned16(views.imgs_tex.detach()), align=16), L.ptr(views.w2c), L.ptr(views.intr), L.ptr(views.c2w), views.nv,
+               L.ptr(plan.b_stream, torch.int32, align=16) if bf16 else L.ptr(plan.t_stream), L.ptr(plan.t_tab), plan.scalars, L.ptr(pts),
                L.ptr(idx, torch.int64), n, L.ptr(count, torch.int32), L.ptr(rgb_out), L.ptr(vis_out, torch.uint8), L.stream(),
-               live=None if count is None else (count, n), nbytes=nbytes, flops=n * flops, label="gens_blend_views")
+               live=None if count is None else (count, n), nbytes=nbytes, flops=n * flops, label=None if bf16 else "gens_blend_views")
         if not plan.finite:
             _poison(idx, count, rgb_out)
         return rgb_out, vis_out

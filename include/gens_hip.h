@@ -544,6 +544,18 @@ int gens_blend_views4(const float* const* feats, const int* hw, int n_levels, co
                       const int64_t* index, int64_t n, const int32_t* n_device, float* rgb_out, uint8_t* vis_out, void* stream);
 int gens_blend_views4_groups(int n_levels);
 
+/* gens_blend_views_t with its large products on the bf16 matrix pipe, float32-accurate (k7b_blend_bf16x3.hip): every float32 operand
+ * is three round-to-nearest bf16 terms, a product the six significant cross terms on v_mfma_f32_16x16x32_bf16 with float32
+ * accumulation; the products with K <= 16 stay on v_mfma_f32_16x16x4_f32.  Same arguments, outputs and limits as gens_blend_views_t
+ * (nv = 3..5, n_levels <= 5) except the stream:
+ *   wstream: DEVICE, 16-byte aligned, (gens_blend_bf16x3_groups(n_levels) + 2) x 3 KB: groups of three 1 KB pieces in consumption
+ *   order (gens_amd.ops._pack_blend_b) -- the three bf16 planes of one (M tile, K block of 32), or float32 fragments in
+ *   gens_blend_views_t's layout (first and last group) -- the two trailing groups zero;  tab, scalars: gens_blend_views_t's. */
+int gens_blend_views_bf16x3(const float* const* feats, const int* hw, int n_levels, const float* imgs, const float* w2c, const float* intr,
+                            const float* c2w, int nv, const void* wstream, const float* tab, const float* scalars, const float* pts,
+                            const int64_t* index, int64_t n, const int32_t* n_device, float* rgb_out, uint8_t* vis_out, void* stream);
+int gens_blend_bf16x3_groups(int n_levels);
+
 /* ------------------------------------------------------------------------------------------------------------
  * K18  lookup_feature + BlendingNetwork.forward of a training / fine-tune step, and their backward
  *      (projector.py:278-349, blending_network.py:69-118 as called from implicit_surface.py:196-199; first order only)
