@@ -18,32 +18,11 @@
 
 #define SPARSE_BLOCK 256
 
-struct SparseBox { float lo[3], hi[3]; };
-
-struct SparseDims {
-    int res, brick, coarse, pbricks;      // R, B, C, P
-};
-
-static inline SparseDims sparse_dims(int res, int brick) {
-    SparseDims d;
-    d.res = res;
-    d.brick = brick;
-    d.coarse = (int)(((int64_t)res + brick - 2) / brick) + 1;
-    d.pbricks = (int)(((int64_t)res + brick - 1) / brick);
-    return d;
-}
-
 // The checks every entry point shares; -> 0 or the error code.
 static int sparse_check(const char* who, int res, int brick) {
     GENS_CHECK_ARG(res >= 2, GENS_EINVAL, "%s: res = %d, at least 2 points per axis", who, res);
     GENS_CHECK_ARG(brick >= 1, GENS_EINVAL, "%s: brick = %d, at least one cell", who, brick);
     GENS_CHECK_ARG((int64_t)res * res * res < ((int64_t)1 << 31), GENS_ELIMIT, "%s: res = %d, res^3 must stay below 2^31 (32-bit point indices)", who, res);
-    return 0;
-}
-
-static int sparse_box(const char* who, const float* bmin3_host, const float* bmax3_host, SparseBox& b) {
-    GENS_CHECK_ARG(bmin3_host && bmax3_host, GENS_EINVAL, "%s: null pointer (bounds)", who);
-    for (int a = 0; a < 3; ++a) { b.lo[a] = bmin3_host[a]; b.hi[a] = bmax3_host[a]; }
     return 0;
 }
 
@@ -65,31 +44,7 @@ __global__ __launch_bounds__(SPARSE_BLOCK) void classify_k(const float* __restri
     if (i >= n) return;
     const uint32_t nb = (uint32_t)c - 1u;
     const uint32_t xy = i / nb, bz = i - xy * nb, bx = xy / nb, by = xy - bx * nb;
-    bool near = false, any_below = false, all_below = true;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const float v = uc[((bx + (k >> 2)) * c + by + ((k >> 1) & 1)) * c + bz + (k & 1)];
-        near = near || !isfinite(v) || fabsf(v - t) <= margin;
-        const bool below = v < t;                     // (a NaN is not below; it made the brick active already)
-        any_below = any_below || below;
-        all_below = all_below && below;
-    }
-    flags[i] = (near || (any_below && !all_below)) ? 1 : 0;
-}
-
-// Row t of a range of listed point bricks -> its UNCLAMPED fine indices; false if the list entry is no point brick (the row is skipped).
-__device__ __forceinline__ bool brick_row(const SparseDims& d, const int64_t* __restrict__ list, uint32_t first, uint32_t t, int& fx, int& fy, int& fz) {
-    const uint32_t b = (uint32_t)d.brick, b3 = b * b * b, p = (uint32_t)d.pbricks;
-    const uint32_t k = t / b3, l = t - k * b3;
-    const int64_t entry = list[first + k];
-    if (entry < 0 || entry >= (int64_t)p * p * p) return false;
-    const uint32_t e = (uint32_t)entry;
-    const uint32_t exy = e / p, ez = e - exy * p, ex = exy / p, ey = exy - ex * p;
-    const uint32_t lxy = l / b, lz = l - lxy * b, lx = lxy / b, ly = lxy - lx * b;
-    fx = (int)(ex * b + lx);
-    fy = (int)(ey * b + ly);
-    fz = (int)(ez * b + lz);
-    return true;
+    flags[i] = brick_is_active(uc, (uint32_t)c, bx, by, bz, t, margin) ? 1 : 0;
 }
 
 __global__ __launch_bounds__(SPARSE_BLOCK) void brick_points_k(SparseBox bx, SparseDims d, const int64_t* __restrict__ list, uint32_t first, uint32_t rows,
@@ -113,9 +68,6 @@ __global__ __launch_bounds__(SPARSE_BLOCK) void scatter_k(const float* __restric
     if (fx >= d.res || fy >= d.res || fz >= d.res) return;                                // a clamped duplicate: its owner wrote the value
     u[((uint32_t)fx * (uint32_t)d.res + (uint32_t)fy) * (uint32_t)d.res + (uint32_t)fz] = -sdf[t];
 }
-
-// the deciding brick's coordinate of fine index i
-__device__ __forceinline__ uint32_t deciding_brick(uint32_t i, uint32_t brick, uint32_t last_brick) { return min(i / brick, last_brick); }
 
 __global__ __launch_bounds__(SPARSE_BLOCK) void fill_k(const float* __restrict__ uc, SparseDims d, uint32_t n, float* __restrict__ u) {
     const uint32_t q = blockIdx.x * SPARSE_BLOCK + threadIdx.x, i0 = q * 4u;

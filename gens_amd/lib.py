@@ -202,6 +202,12 @@ SIGNATURES = {
     "gens_sparse_fill": [_p, _i, _i, _p, _p],
     "gens_sparse_scatter": [_p, _i, _i, _p, _l, _l, _l, _p, _p],
     "gens_sparse_leaks": [_p, _i, _i, _p, _f, _p, _p],
+    "gens_brick_coarse_points": [_fp, _fp, _i, _i, _l, _l, _p, _p],
+    "gens_brick_points": [_fp, _fp, _i, _i, _p, _l, _l, _l, _p, _p],
+    "gens_brick_active": [_p, _i, _i, _f, _f, _p, _p],
+    "gens_brick_emit_flags": [_p, _i, _i, _p, _p],
+    "gens_brick_mc_classify": [_p, _p, _p, _p, _i, _i, _p, _l, _f, _p, _p, _p, _p, _p, _p],
+    "gens_brick_mc_emit": [_p, _p, _p, _p, _i, _i, _p, _l, _f, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
 }
 
 _lib = None

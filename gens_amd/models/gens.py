@@ -94,6 +94,9 @@ class GenS(nn.Module):
         brick = confs.get("sparse_lattice", None)               # optional: extract_geometry's two-level lattice (a brick edge, or True)
         if brick is not None:
             self.implicit_surface.sparse_lattice = brick if isinstance(brick, bool) else int(brick)
+        mesh = confs.get("sparse_mesh", None)                   # optional: marching cubes on that lattice's bricks, no dense lattice (K29)
+        if mesh is not None:
+            self.implicit_surface.sparse_mesh = bool(mesh)
         lipschitz = confs.get("lattice_lipschitz", None)        # optional: the bound that lattice assumes (ImplicitSurface.lattice_lipschitz)
         if lipschitz is not None:
             self.implicit_surface.lattice_lipschitz = float(lipschitz)

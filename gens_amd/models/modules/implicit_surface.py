@@ -573,6 +573,8 @@ class ImplicitSurface(nn.Module):
                                    # the leak count of every sparse call checks it and falls back to the dense lattice when it fails
     last_lattice_stats = None      # ops.sparse_lattice's stats of the last sdf_grid call (None: that call was dense)
     SPARSE_BRICK = 4               # what `sparse=True` means: the brick edge that measured best at 512^3 and 1024^3
+    sparse_mesh = None             # True: extract_geometry runs marching cubes on the sparse lattice's bricks (ops.brick_marching_cubes, K29) and
+                                   # builds no dense lattice; needs a sparse brick of 2 to 8 cells.  None / False: off
 
     def _lattice_brick(self, sparse, shard):
         """The brick edge of this call, or None for the dense lattice.  sparse: None = the attribute `sparse_lattice`, False = dense."""
@@ -591,6 +593,25 @@ class ImplicitSurface(nn.Module):
             return None
         return brick
 
+    def _lattice_passes(self, vols, shard, run):
+        """run(evaluate) with the lattice's evaluator (the fused plan and this scene's precision, else the PyTorch layers) -> its result.  A
+        split-half launch that met a value outside the half range repeats the WHOLE run in float32, like the image."""
+        split_half = None
+        for _ in range(2):
+            def evaluate(pts):
+                plan = self._fused_plan(vols)
+                prec = "f32" if split_half is False else self._precision(plan) if plan is not None else "f32"
+                return ops.sdf_mlp(plan, vols, pts, precision=prec) if plan is not None else self.sdf_network.sdf(pts, vols)
+
+            out = run(evaluate)
+            overflowed = split_half is not False and self._split_half_overflowed()
+            if shard is not None and split_half is not False and self.sdf_precision == "f16x2":
+                overflowed = shard.any(overflowed)
+            if not overflowed:
+                break
+            split_half = False
+        return out
+
     @torch.no_grad()
     def sdf_grid(self, volumes, bound_min, bound_max, resolution, chunk=1 << 21, shard=None, sparse=None, threshold=0.0):
         """u = -sdf on the resolution^3 lattice (:407-421), kept on the device.  shard (gens_amd.distributed.Shard): this rank evaluates
@@ -607,33 +628,24 @@ class ImplicitSurface(nn.Module):
         self.last_lattice_stats = None
         if brick is None:
             u = torch.zeros(len(own), chunk, device=dev) if shard is not None else torch.empty(total, device=dev)
-        split_half = None                              # a value outside the half range: the lattice again in float32, like the image
-        for attempt in range(2):
-            def evaluate(pts):
-                plan = self._fused_plan(vols)
-                prec = "f32" if split_half is False else self._precision(plan) if plan is not None else "f32"
-                return ops.sdf_mlp(plan, vols, pts, precision=prec) if plan is not None else self.sdf_network.sdf(pts, vols)
 
+        def run(evaluate):
             if brick is not None:                      # coarse and fine passes together; an overflow repeats both
-                u, self.last_lattice_stats = ops.sparse_lattice(evaluate, bound_min.tolist(), bound_max.tolist(), resolution, threshold, brick,
-                                                                self.lattice_lipschitz, chunk=chunk, device=dev)
-                u = u.reshape(-1)
-            else:
-                for k, c in enumerate(own):
-                    first = c * chunk
-                    count = min(chunk, total - first)
-                    pts = ops.lattice_points(bound_min.tolist(), bound_max.tolist(), resolution, first, count, dev)
-                    sdf = evaluate(pts)
-                    if shard is not None:
-                        u[k, :count] = -sdf[:, 0]
-                    else:
-                        u[first:first + count] = -sdf[:, 0]
-            overflowed = split_half is not False and self._split_half_overflowed()
-            if shard is not None and split_half is not False and self.sdf_precision == "f16x2":
-                overflowed = shard.any(overflowed)
-            if not overflowed:
-                break
-            split_half = False
+                us, self.last_lattice_stats = ops.sparse_lattice(evaluate, bound_min.tolist(), bound_max.tolist(), resolution, threshold, brick,
+                                                                 self.lattice_lipschitz, chunk=chunk, device=dev)
+                return us.reshape(-1)
+            for k, c in enumerate(own):
+                first = c * chunk
+                count = min(chunk, total - first)
+                pts = ops.lattice_points(bound_min.tolist(), bound_max.tolist(), resolution, first, count, dev)
+                sdf = evaluate(pts)
+                if shard is not None:
+                    u[k, :count] = -sdf[:, 0]
+                else:
+                    u[first:first + count] = -sdf[:, 0]
+            return u
+
+        u = self._lattice_passes(vols, shard, run)
         if shard is not None:
             u = shard.gather_chunks(u, n_chunks)
             if u is None:
@@ -641,14 +653,73 @@ class ImplicitSurface(nn.Module):
             u = u.reshape(-1)[:total]
         return u.reshape(resolution, resolution, resolution)
 
-    def extract_geometry(self, volumes, bound_min, bound_max, resolution, threshold, shard=None, sparse=None):
+    def _mesh_brick(self, sparse, sparse_mesh, shard):
+        """The brick edge of a brick-sparse extraction (K29), or None for the lattice route.  sparse_mesh: None = the attribute."""
+        if sparse_mesh is None:
+            sparse_mesh = self.sparse_mesh
+        if not sparse_mesh:
+            return None
+        if sparse is None:
+            sparse = self.sparse_lattice
+        if sparse is None or sparse is False:
+            raise ValueError("sparse_mesh needs the sparse lattice: pass sparse (a brick edge of 2 to 8 cells, or True) or set `sparse_lattice`")
+        if shard is not None:                          # (before the brick is looked at: with a shard the option is not in effect)
+            if not getattr(self, "_warned_sparse_mesh_shard", False):
+                import warnings
+                warnings.warn("gens_amd: sparse_mesh is not sharded: with a shard the lattice is gathered and marching cubes runs on it",
+                              RuntimeWarning, stacklevel=3)
+                self._warned_sparse_mesh_shard = True
+            return None
+        brick = self.SPARSE_BRICK if sparse is True else int(sparse)
+        if not 2 <= brick <= ops.BRICK_MC_MAX:
+            raise ValueError(f"sparse_mesh: sparse = {sparse!r}, the brick-sparse marching cubes takes bricks of 2 to {ops.BRICK_MC_MAX} cells")
+        return brick
+
+    @torch.no_grad()
+    def _brick_mesh(self, volumes, bound_min, bound_max, resolution, threshold, brick):
+        """Vertices (index coordinates) and triangles on the device through ops.brick_marching_cubes; None if the leak count refutes the bound
+        `lattice_lipschitz` and the dense lattice can still be built (the caller takes that route); RuntimeError if it cannot."""
+        import warnings
+        vols = volumes if isinstance(volumes, ops.VolumeSet) else ops.VolumeSet.packed(volumes)
+        dev = vols.tensors[0].device
+        lo, hi = bound_min.tolist(), bound_max.tolist()
+        vertices, triangles, stats = self._lattice_passes(vols, None, lambda evaluate: ops.brick_marching_cubes(
+            evaluate, lo, hi, resolution, threshold, brick, self.lattice_lipschitz, device=dev))
+        self.last_lattice_stats = stats
+        if not stats["leaks"]:
+            return vertices, triangles
+        dense_fits = resolution ** 3 < 1 << 31
+        warnings.warn(f"sparse_mesh: {stats['leaks']} lattice edges cross the threshold {float(threshold)!r} next to an inactive brick, so the field "
+                      f"is not {float(self.lattice_lipschitz)!r}-Lipschitz on this lattice (resolution {resolution}, brick {brick}); "
+                      + ("extracting from the dense lattice instead" if dense_fits else "there is no dense lattice at this resolution"),
+                      RuntimeWarning, stacklevel=4)
+        if not dense_fits:
+            raise RuntimeError(f"sparse_mesh: {stats['leaks']} leaks at resolution {resolution}: the mesh would have holes, and {resolution}^3 points "
+                               "are beyond the dense lattice (2^31): raise lattice_lipschitz")
+        return None
+
+    def extract_geometry(self, volumes, bound_min, bound_max, resolution, threshold, shard=None, sparse=None, sparse_mesh=None):
         """-> vertices (V,3) float64, triangles (T,3) int32 as numpy arrays (implicit_surface.py:407-427).  The SDF lattice and
         the marching cubes both run on the device (the reference: 512 D2H copies + PyMCubes on the host); only the mesh is copied.
-        sparse: sdf_grid's option of that name, with this call's threshold."""
-        u = self.sdf_grid(volumes, bound_min, bound_max, resolution, shard=shard, sparse=sparse, threshold=threshold)
-        if u is None:
-            return None, None
-        vertices, triangles = ops.marching_cubes(u, threshold)
+        sparse: sdf_grid's option of that name, with this call's threshold.  sparse_mesh (default: the attribute of that name, None = off):
+        together with a sparse brick of 2 to 8 cells, marching cubes runs on the bricks (ops.brick_marching_cubes) and no dense lattice is
+        built -- the same mesh, resolutions beyond 1290 included.  A leak count above zero warns and takes the dense lattice (RuntimeError
+        where resolution^3 >= 2^31 leaves none); with a shard the option is ignored with one warning."""
+        brick = self._mesh_brick(sparse, sparse_mesh, shard)
+        mesh = None
+        if brick is not None:
+            mesh = self._brick_mesh(volumes, bound_min, bound_max, resolution, threshold, brick)
+            if mesh is None:                           # the bound failed: the dense lattice, evaluated once
+                stats = self.last_lattice_stats
+                u = self.sdf_grid(volumes, bound_min, bound_max, resolution, shard=None, sparse=False, threshold=threshold)
+                self.last_lattice_stats = {**stats, "evaluated_points": stats["evaluated_points"] + resolution ** 3, "fell_back": True}
+                mesh = ops.marching_cubes(u, threshold)
+        else:
+            u = self.sdf_grid(volumes, bound_min, bound_max, resolution, shard=shard, sparse=sparse, threshold=threshold)
+            if u is None:
+                return None, None
+            mesh = ops.marching_cubes(u, threshold)
+        vertices, triangles = mesh
         vertices, triangles = vertices.cpu().numpy(), triangles.cpu().numpy()
         b_max, b_min = bound_max.detach().cpu().numpy(), bound_min.detach().cpu().numpy()
         vertices = vertices / (resolution - 1.0) * (b_max - b_min)[None, :] + b_min[None, :]
@@ -656,11 +727,13 @@ class ImplicitSurface(nn.Module):
 
     @torch.no_grad()
     def validate(self, rays_o, rays_d, near, far, volumes, mask_volumes, imgs, features, match_features, intrs, c2ws, bound_min, bound_max,
-                 hw, cos_anneal_ratio=1.0, step=None, extract_geometry=True, mesh_resolution=512, threshold=0.0, scene=None, shard=None, sparse=None):
+                 hw, cos_anneal_ratio=1.0, step=None, extract_geometry=True, mesh_resolution=512, threshold=0.0, scene=None, shard=None, sparse=None,
+                 sparse_mesh=None):
         """shard (gens_amd.distributed.Shard, optional): render only this rank's contiguous ray range and evaluate only its lattice
         chunks; the (P, 8) image buffer / the lattice slabs are gathered over RCCL, so every rank returns the whole image.  The jitter
         of EVERY ray is drawn on every rank from the identically seeded CPU generator (the reference's draw order) and sliced with
-        the rays: the image does not depend on the partition.  sparse: extract_geometry's option (the two-level lattice)."""
+        the rays: the image does not depend on the partition.  sparse, sparse_mesh: extract_geometry's options (the two-level lattice, marching cubes
+        on its bricks)."""
         outputs = {}
         if scene is None:
             scene = Scene(volumes, mask_volumes, imgs, features, match_features, intrs, c2ws)
@@ -680,7 +753,8 @@ class ImplicitSurface(nn.Module):
             import time
             t_geo = time.perf_counter()
             outputs["vertices"], outputs["triangles"] = self.extract_geometry(scene.volumes_nograd(), bound_min, bound_max, mesh_resolution,
-                                                                              threshold, shard=shard, sparse=sparse)
+                                                                              threshold, shard=shard, sparse=sparse,
+                                                                              sparse_mesh=sparse_mesh)
             self.last_geometry_s = time.perf_counter() - t_geo     # (ends with the mesh's read-back: wall time is the item's share; bench.py's default_path)
         # one (P, 8) device buffer [rgb | normal | sdf_depth | render_depth] filled chunk by chunk: ONE D2H copy per image
         # into a pinned host buffer (the reference copies 4 tensors per 256-ray chunk, implicit_surface.py:446-453)

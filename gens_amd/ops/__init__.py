@@ -22,6 +22,7 @@ is what it was when ops was one module:
     ops.filter    K26: the mask pyramid restricted to the dilated SDF band (GenS.filter_volume, models/gens.py:87-122);
                   K27: the largest connected region of a mask volume (clean_volume, utils/tools.py:34-50).
     ops.lattice   K28: the two-level SDF lattice of extract_geometry, evaluated near the iso-surface only (sparse_lattice).
+    ops.brick_mcubes  K29: marching cubes on that lattice's bricks, without the dense lattice (brick_marching_cubes).
 """
 from .base import *  # noqa: F401,F403
 from .volume import *  # noqa: F401,F403
@@ -37,3 +38,4 @@ from .points import *  # noqa: F401,F403
 from .finalize import *  # noqa: F401,F403
 from .filter import *  # noqa: F401,F403
 from .lattice import *  # noqa: F401,F403
+from .brick_mcubes import *  # noqa: F401,F403

@@ -21,14 +21,19 @@ def lattice_points(bound_min, bound_max, resolution, first, count, device):
 _MC_TABLES = {}
 
 
+def _mc_tables(dev):
+    """The case table (256, 16) int8 and the triangle counts (256,) uint8 of gens_amd/mc_tables.py on `dev`, copied there once."""
+    from .. import mc_tables
+    if dev not in _MC_TABLES:
+        _MC_TABLES[dev] = (torch.from_numpy(mc_tables.TRI_TABLE.copy()).to(dev), torch.from_numpy(mc_tables.TRI_COUNT.copy()).to(dev))
+    return _MC_TABLES[dev]
+
+
 def marching_cubes(u, threshold=0.0):
     """u (X,Y,Z) float32 device tensor -> (vertices (V,3) float64 in index coordinates, triangles (T,3) int32), both on the
     device.  Classic marching cubes with the case table of gens_amd/mc_tables.py; order as in oracle/mc_oracle.py."""
-    from .. import mc_tables
     dev = u.device
-    if dev not in _MC_TABLES:
-        _MC_TABLES[dev] = (torch.from_numpy(mc_tables.TRI_TABLE.copy()).to(dev), torch.from_numpy(mc_tables.TRI_COUNT.copy()).to(dev))
-    table, count = _MC_TABLES[dev]
+    table, count = _mc_tables(dev)
     u = _c(u.detach().to(_f32))
     x, y, z = u.shape
     total = x * y * z

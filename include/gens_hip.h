@@ -60,7 +60,8 @@ const char* gens_last_error(void);
  *       gens_mesh_sample_{count,emit}, gens_point_grid_{count,fill}, gens_radius_downsample_round, gens_nearest_point, and K25's
  *       gens_dilate_u8, gens_vertex_mask_votes, gens_view_rays_hit_counts, and K26's gens_filter_masks, gens_filter_band, gens_filter_levels,
  *       and K27's gens_largest_component, gens_components_scratch_bytes, gens_unpack_mask_bits, and K28's gens_sparse_coarse_points,
- *       gens_sparse_classify, gens_sparse_brick_points, gens_sparse_fill, gens_sparse_scatter, gens_sparse_leaks. */
+ *       gens_sparse_classify, gens_sparse_brick_points, gens_sparse_fill, gens_sparse_scatter, gens_sparse_leaks, and K29's
+ *       gens_brick_coarse_points, gens_brick_points, gens_brick_active, gens_brick_emit_flags, gens_brick_mc_classify, gens_brick_mc_emit. */
 int gens_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -865,6 +866,43 @@ int gens_sparse_fill(const float* uc, int res, int brick, float* u, void* stream
 int gens_sparse_scatter(const float* sdf, int res, int brick, const int64_t* list, int64_t n_list, int64_t first, int64_t count, float* u,
                         void* stream);
 int gens_sparse_leaks(const float* u, int res, int brick, const uint8_t* flags, float t, int64_t* leaks, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * K29  Marching cubes on the bricks of K28's two-level lattice (ops.brick_marching_cubes): the mesh gens_mc_classify / gens_mc_emit return
+ *      for the lattice K28 builds, without that lattice.  K28's terms (R, B, C, P, deciding and point bricks, the active rule, the fill =
+ *      uc at the deciding brick's lowest corner, the leak rule) hold unchanged; u = -sdf.
+ *   Limits: res = R >= 2, 2 <= brick = B <= 8 (GENS_EINVAL); C^3 < 2^31 and P^3 < 2^31 (GENS_ELIMIT) -- not R^3.  Per-axis indices are
+ *   32-bit, flat fine-lattice indices (the keys) 64-bit.  Arguments are checked before any launch; every pointer non-null unless the list
+ *   or range is empty.
+ *     gens_brick_coarse_points / gens_brick_points: gens_sparse_coarse_points / gens_sparse_brick_points under these limits, bit-equal to
+ *       gens_lattice_points at the same per-axis index; count < 2^31 / 3 rows per call.
+ *     gens_brick_active: gens_sparse_classify's rule: uc (C^3) -> flags ((C - 1)^3) bytes.
+ *     gens_brick_emit_flags: emit[X] = 1 if a brick of X + {0,1}^3 (clipped to the (C - 1)^3 grid) is active.  Every cell of K28's lattice
+ *       with corners on both sides of t, and every crossing edge, starts at a point decided by such a brick.
+ *   The per-brick calls take `list`: n_list (< 2^31) int64 point-brick numbers on the DEVICE, the point bricks whose deciding brick emits
+ *   (an entry outside the P^3 grid emits nothing); entry k owns rows k * B^3 .. of the per-point arrays, brick-local C order.
+ *   store: (evaluated point bricks, B^3) u in gens_brick_points' row order; pslot (P^3) int32: a point brick's row of store or -1.
+ *     gens_brick_mc_classify: per point vmask / cases as gens_mc_classify defines them (0 for an index past R - 1) and rank (uint16) = the
+ *       vertices of the brick's earlier points; counts (3, n_list) int32 = the bricks' vertices, triangles and leaks (gens_sparse_leaks'
+ *       rule on the edges its points own).  tri_count: the 256 bytes of gens_mc_classify.
+ *     gens_brick_mc_emit: voff / toff (n_list) int64 = exclusive scans of the counts; eslot (P^3) int32: a point brick's index in `list`
+ *       or -1.  Vertex of edge (p, a): gens_mc_emit's float64 expression, at voff[brick] + rank (+ earlier axes); vkey = 3 flat(p) + a.
+ *       Triangles (vertex ids through eslot; -1 for an owner outside the list, which the covering argument excludes) at toff[brick] + the
+ *       triangles of the brick's earlier points; tkey = flat(cell).  Sorting by the keys gives gens_mc_emit's order.
+ * ---------------------------------------------------------------------------------------------------------- */
+int gens_brick_coarse_points(const float* bmin3_host, const float* bmax3_host, int res, int brick, int64_t first, int64_t count, float* pts,
+                             void* stream);
+int gens_brick_points(const float* bmin3_host, const float* bmax3_host, int res, int brick, const int64_t* list, int64_t n_list, int64_t first,
+                      int64_t count, float* pts, void* stream);
+int gens_brick_active(const float* uc, int res, int brick, float t, float margin, uint8_t* flags, void* stream);
+int gens_brick_emit_flags(const uint8_t* active, int res, int brick, uint8_t* emit, void* stream);
+int gens_brick_mc_classify(const float* uc, const float* store, const int32_t* pslot, const uint8_t* active, int res, int brick,
+                           const int64_t* list, int64_t n_list, float iso, const uint8_t* tri_count, uint8_t* vmask, uint8_t* cases,
+                           uint16_t* rank, int32_t* counts, void* stream);
+int gens_brick_mc_emit(const float* uc, const float* store, const int32_t* pslot, const int32_t* eslot, int res, int brick, const int64_t* list,
+                       int64_t n_list, float iso, const int8_t* tri_table, int table_stride, const uint8_t* tri_count, const uint8_t* vmask,
+                       const uint8_t* cases, const uint16_t* rank, const int64_t* voff, const int64_t* toff, double* vertices,
+                       int32_t* triangles, int64_t* vkey, int64_t* tkey, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K14  C (m x n) = A^T B for tall row-major operands A (k x m), B (k x n), k >> m, n: the weight-gradient product of the training
