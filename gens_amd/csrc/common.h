@@ -91,64 +91,6 @@ __device__ __forceinline__ float linspace_at(float start, float end, int steps, 
     return (i < steps / 2) ? start + step * (float)i : end - step * (float)(steps - 1 - i);
 }
 
-// The two-level lattice shared by K28 (k28_sparse_lattice.hip, whose header comment defines the terms) and K29 (k29_brick_mcubes.hip).
-struct SparseBox { float lo[3], hi[3]; };
-
-struct SparseDims {
-    int res, brick, coarse, pbricks;      // R, B, C, P
-};
-
-static inline SparseDims sparse_dims(int res, int brick) {
-    SparseDims d;
-    d.res = res;
-    d.brick = brick;
-    d.coarse = (int)(((int64_t)res + brick - 2) / brick) + 1;
-    d.pbricks = (int)(((int64_t)res + brick - 1) / brick);
-    return d;
-}
-
-static int sparse_box(const char* who, const float* bmin3_host, const float* bmax3_host, SparseBox& b) {
-    GENS_CHECK_ARG(bmin3_host && bmax3_host, GENS_EINVAL, "%s: null pointer (bounds)", who);
-    for (int a = 0; a < 3; ++a) { b.lo[a] = bmin3_host[a]; b.hi[a] = bmax3_host[a]; }
-    return 0;
-}
-
-// the deciding brick's coordinate of fine index i
-__device__ __forceinline__ uint32_t deciding_brick(uint32_t i, uint32_t brick, uint32_t last_brick) { return min(i / brick, last_brick); }
-
-// Row t of a range of listed point bricks -> its UNCLAMPED fine indices; false if the list entry is no point brick (the row is skipped).
-__device__ __forceinline__ bool brick_row(const SparseDims& d, const int64_t* __restrict__ list, uint32_t first, uint32_t t, int& fx, int& fy, int& fz) {
-    const uint32_t b = (uint32_t)d.brick, b3 = b * b * b, p = (uint32_t)d.pbricks;
-    const uint32_t k = t / b3, l = t - k * b3;
-    const int64_t entry = list[first + k];
-    if (entry < 0 || entry >= (int64_t)p * p * p) return false;
-    const uint32_t e = (uint32_t)entry;
-    const uint32_t exy = e / p, ez = e - exy * p, ex = exy / p, ey = exy - ex * p;
-    const uint32_t lxy = l / b, lz = l - lxy * b, lx = lxy / b, ly = lxy - lx * b;
-    fx = (int)(ex * b + lx);
-    fy = (int)(ey * b + ly);
-    fz = (int)(ez * b + lz);
-    return true;
-}
-
-// The ACTIVE rule of brick (bx, by, bz) on the coarse values uc (c^3): a corner non-finite or within margin of t, or the corners disagree.
-__device__ __forceinline__ bool brick_is_active(const float* __restrict__ uc, uint32_t c, uint32_t bx, uint32_t by, uint32_t bz, float t, float margin) {
-    bool near = false, any_below = false, all_below = true;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const float v = uc[((bx + (k >> 2)) * c + by + ((k >> 1) & 1)) * c + bz + (k & 1)];
-        near = near || !isfinite(v) || fabsf(v - t) <= margin;
-        const bool below = v < t;                     // (a NaN is not below; it made the brick active already)
-        any_below = any_below || below;
-        all_below = all_below && below;
-    }
-    return near || (any_below && !all_below);
-}
-
-// Marching cubes (K12, K29): edge of a cell in Bourke's numbering -> (offset of the lattice point that owns it, axis)
-[[maybe_unused]] static __device__ __constant__ int c_edge_owner[12][4] = {{0, 0, 0, 0}, {1, 0, 0, 1}, {0, 1, 0, 0}, {0, 0, 0, 1}, {0, 0, 1, 0}, {1, 0, 1, 1},
-                                                                           {0, 1, 1, 0}, {0, 0, 1, 1}, {0, 0, 0, 2}, {1, 0, 0, 2}, {1, 1, 0, 2}, {0, 1, 0, 2}};
-
 // Union-find on int32 parents shared by K23 (faces of a mesh) and K27 (voxels of a bit volume).
 __device__ __forceinline__ int32_t parent_load(int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 

@@ -1,4 +1,5 @@
 // K28: the two-level lattice of extract_geometry (implicit_surface.py:407-427) -- the SDF network evaluated near the iso-surface only.
+// (The definitions K29 shares -- dimensions, limits, the deciding brick, the ACTIVE and the leak rule -- are lattice.h's.)
 // res points per axis, bricks of `brick` cells; C = ceil((res - 1) / brick) + 1 coarse points per axis, coarse index i = fine index
 // min(i * brick, res - 1); (C - 1)^3 bricks, brick b between the coarse points b and b + 1 of every axis.  Six streaming launches around the
 // caller's evaluator (ops.sparse_lattice):
@@ -14,17 +15,12 @@
 // duplicate that the scatter drops.  The brick that DECIDES for fine index i is min(i / brick, C - 2).
 // Coordinates are linspace_at's, K11's formula: the points are bit-equal to gens_lattice_points' at the same fine indices.
 // All indices are 32-bit (res^3 < 2^31, checked): the per-thread decode is a handful of 32-bit divisions, no 64-bit arithmetic.
-#include "common.h"
+// coarse_points_k, classify_k and brick_points_k also serve K29's entry points (gens_brick_coarse_points, gens_brick_active,
+// gens_brick_points) under K29's limits, where res^3 may pass 2^31: they index only the coarse grid (C^3), the point-brick grid (P^3) and
+// the rows of one call (fewer than 2^31 / 3) in 32 bits and a fine index per AXIS, never a flat fine index, so they are correct under both.
+#include "lattice.h"
 
 #define SPARSE_BLOCK 256
-
-// The checks every entry point shares; -> 0 or the error code.
-static int sparse_check(const char* who, int res, int brick) {
-    GENS_CHECK_ARG(res >= 2, GENS_EINVAL, "%s: res = %d, at least 2 points per axis", who, res);
-    GENS_CHECK_ARG(brick >= 1, GENS_EINVAL, "%s: brick = %d, at least one cell", who, brick);
-    GENS_CHECK_ARG((int64_t)res * res * res < ((int64_t)1 << 31), GENS_ELIMIT, "%s: res = %d, res^3 must stay below 2^31 (32-bit point indices)", who, res);
-    return 0;
-}
 
 __global__ __launch_bounds__(SPARSE_BLOCK) void coarse_points_k(SparseBox b, SparseDims d, uint32_t first, uint32_t count, float* __restrict__ pts) {
     const uint32_t t = blockIdx.x * SPARSE_BLOCK + threadIdx.x;
@@ -52,11 +48,12 @@ __global__ __launch_bounds__(SPARSE_BLOCK) void brick_points_k(SparseBox bx, Spa
     const uint32_t t = blockIdx.x * SPARSE_BLOCK + threadIdx.x;
     if (t >= rows) return;
     int fx = 0, fy = 0, fz = 0;
-    (void)brick_row(d, list, first, t, fx, fy, fz);         // (a bad entry: the first lattice point, a row the scatter skips too)
+    (void)brick_row(d, list, first, t, fx, fy, fz);         // (a bad entry: the first lattice point, a row no caller keeps)
     const int last = d.res - 1;
-    pts[3 * t] = linspace_at(bx.lo[0], bx.hi[0], d.res, min(fx, last));
-    pts[3 * t + 1] = linspace_at(bx.lo[1], bx.hi[1], d.res, min(fy, last));
-    pts[3 * t + 2] = linspace_at(bx.lo[2], bx.hi[2], d.res, min(fz, last));
+    float* p = pts + (size_t)3 * t;
+    p[0] = linspace_at(bx.lo[0], bx.hi[0], d.res, min(fx, last));
+    p[1] = linspace_at(bx.lo[1], bx.hi[1], d.res, min(fy, last));
+    p[2] = linspace_at(bx.lo[2], bx.hi[2], d.res, min(fz, last));
 }
 
 __global__ __launch_bounds__(SPARSE_BLOCK) void scatter_k(const float* __restrict__ sdf, SparseDims d, const int64_t* __restrict__ list, uint32_t first,
@@ -98,47 +95,41 @@ __global__ __launch_bounds__(SPARSE_BLOCK) void leaks_k(const float* __restrict_
     const uint32_t i = blockIdx.x * SPARSE_BLOCK + threadIdx.x;
     uint32_t mine = 0;
     if (i < n) {
-        const uint32_t r = (uint32_t)d.res, b = (uint32_t)d.brick, nb = (uint32_t)d.coarse - 1u, lb = nb - 1u;
+        const uint32_t r = (uint32_t)d.res;
         const uint32_t xy = i / r, kz = i - xy * r, ix = xy / r, jy = xy - ix * r;
         const bool below = u[i] < t;
         const uint32_t step[3] = {r * r, r, 1u}, at[3] = {ix, jy, kz};
-        bool own_known = false, own_active = false;
+        uint32_t m = 0;
 #pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            if (at[a] + 1u >= r) continue;
-            if ((u[i + step[a]] < t) == below) continue;
-            if (!own_known) {                              // crossing edges are rare: the flags are read for those only
-                own_active = flags[(deciding_brick(ix, b, lb) * nb + deciding_brick(jy, b, lb)) * nb + deciding_brick(kz, b, lb)] != 0;
-                own_known = true;
-            }
-            const uint32_t qx = ix + (a == 0), qy = jy + (a == 1), qz = kz + (a == 2);
-            const bool other_active = flags[(deciding_brick(qx, b, lb) * nb + deciding_brick(qy, b, lb)) * nb + deciding_brick(qz, b, lb)] != 0;
-            if (!own_active || !other_active) ++mine;
-        }
+        for (int a = 0; a < 3; ++a)
+            if (at[a] + 1u < r && (u[i + step[a]] < t) != below) m |= 1u << a;
+        if (m) mine = leaking_edges(flags, d, ix, jy, kz, m);       // crossing edges are rare: the flags are read for those only
     }
     // one atomic per wave that found something: a thread counts 0 to 3 edges: one ballot per bit of that
     const unsigned long long b0 = __ballot(mine & 1u), b1 = __ballot(mine & 2u);
     if ((threadIdx.x & 63) == 0 && (b0 | b1)) atomicAdd(leaks, (unsigned long long)(__popcll(b0) + 2 * __popcll(b1)));
 }
 
-extern "C" int gens_sparse_coarse_points(const float* bmin3_host, const float* bmax3_host, int res, int brick, int64_t first, int64_t count,
-                                         float* pts, void* stream) {
-    const char* who = "gens_sparse_coarse_points";
-    if (int e = sparse_check(who, res, brick)) return e;
+// The launchers of the three kernels both families share: `who` is the entry point, `limits` its set of limits.
+static int launch_coarse_points(const char* who, LatticeLimits limits, const float* bmin3_host, const float* bmax3_host, int res, int brick, int64_t first,
+                                int64_t count, float* pts, void* stream) {
+    if (int e = lattice_check(who, res, brick, limits)) return e;
     SparseBox b;
     if (int e = sparse_box(who, bmin3_host, bmax3_host, b)) return e;
     const SparseDims d = sparse_dims(res, brick);
-    GENS_CHECK_ARG(first >= 0 && count >= 0 && first + count <= (int64_t)d.coarse * d.coarse * d.coarse, GENS_EINVAL,
-                   "%s: range [%lld, %lld) beyond the %d^3 coarse points", who, (long long)first, (long long)(first + count), d.coarse);
+    const int64_t n = (int64_t)d.coarse * d.coarse * d.coarse;
+    GENS_CHECK_ARG(first >= 0 && count >= 0 && first <= n && count <= n - first, GENS_EINVAL, "%s: range [%lld, %lld + %lld) beyond the %d^3 coarse points",
+                   who, (long long)first, (long long)first, (long long)count, d.coarse);
+    GENS_CHECK_ARG(limits == LATTICE_K28 || count < ((int64_t)1 << 31) / 3, GENS_ELIMIT, "%s: %lld points: fewer than 2^31 / 3 per call", who,
+                   (long long)count);
     if (count == 0) return 0;
     GENS_CHECK_ARG(pts, GENS_EINVAL, "%s: null pointer (pts)", who);
     coarse_points_k<<<gens_blocks(count, SPARSE_BLOCK), SPARSE_BLOCK, 0, (hipStream_t)stream>>>(b, d, (uint32_t)first, (uint32_t)count, pts);
     return gens_launch_status(who);
 }
 
-extern "C" int gens_sparse_classify(const float* uc, int res, int brick, float t, float margin, uint8_t* flags, void* stream) {
-    const char* who = "gens_sparse_classify";
-    if (int e = sparse_check(who, res, brick)) return e;
+static int launch_classify(const char* who, LatticeLimits limits, const float* uc, int res, int brick, float t, float margin, uint8_t* flags, void* stream) {
+    if (int e = lattice_check(who, res, brick, limits)) return e;
     GENS_CHECK_ARG(uc && flags, GENS_EINVAL, "%s: null pointer", who);
     GENS_CHECK_ARG(margin >= 0.0f, GENS_EINVAL, "%s: margin = %g, must be >= 0 (and no NaN)", who, (double)margin);
     const SparseDims d = sparse_dims(res, brick);
@@ -147,37 +138,51 @@ extern "C" int gens_sparse_classify(const float* uc, int res, int brick, float t
     return gens_launch_status(who);
 }
 
-// The list range of the two per-brick entry points -> rows (brick^3 per entry), or an error code.
-static int sparse_rows(const char* who, const SparseDims& d, const int64_t* list, int64_t n_list, int64_t first, int64_t count, int64_t& rows) {
-    GENS_CHECK_ARG(n_list >= 0 && first >= 0 && count >= 0 && first + count <= n_list, GENS_EINVAL, "%s: range [%lld, %lld) beyond the list of %lld bricks",
-                   who, (long long)first, (long long)(first + count), (long long)n_list);
-    GENS_CHECK_ARG(d.brick <= 1024 && count < ((int64_t)1 << 31), GENS_ELIMIT, "%s: brick = %d (at most 1024), %lld bricks (fewer than 2^31)", who, d.brick,
-                   (long long)count);
-    rows = count * d.brick * d.brick * d.brick;
-    GENS_CHECK_ARG(first < ((int64_t)1 << 31) && rows < ((int64_t)1 << 31) / 3, GENS_ELIMIT, "%s: %lld bricks of %d^3 points: fewer than 2^31 / 3 rows per call",
-                   who, (long long)count, d.brick);
-    GENS_CHECK_ARG(count == 0 || list, GENS_EINVAL, "%s: null pointer (list)", who);
-    return 0;
+static int launch_brick_points(const char* who, LatticeLimits limits, const float* bmin3_host, const float* bmax3_host, int res, int brick,
+                               const int64_t* list, int64_t n_list, int64_t first, int64_t count, float* pts, void* stream) {
+    if (int e = lattice_check(who, res, brick, limits)) return e;
+    SparseBox b;
+    if (int e = sparse_box(who, bmin3_host, bmax3_host, b)) return e;
+    if (int e = lattice_range(who, limits, brick, list, n_list, first, count, true)) return e;
+    if (count == 0) return 0;
+    GENS_CHECK_ARG(pts, GENS_EINVAL, "%s: null pointer (pts)", who);
+    const int64_t rows = count * brick * brick * brick;
+    brick_points_k<<<gens_blocks(rows, SPARSE_BLOCK), SPARSE_BLOCK, 0, (hipStream_t)stream>>>(b, sparse_dims(res, brick), list, (uint32_t)first, (uint32_t)rows,
+                                                                                            pts);
+    return gens_launch_status(who);
+}
+
+extern "C" int gens_sparse_coarse_points(const float* bmin3_host, const float* bmax3_host, int res, int brick, int64_t first, int64_t count,
+                                         float* pts, void* stream) {
+    return launch_coarse_points("gens_sparse_coarse_points", LATTICE_K28, bmin3_host, bmax3_host, res, brick, first, count, pts, stream);
+}
+
+extern "C" int gens_brick_coarse_points(const float* bmin3_host, const float* bmax3_host, int res, int brick, int64_t first, int64_t count,
+                                        float* pts, void* stream) {
+    return launch_coarse_points("gens_brick_coarse_points", LATTICE_K29, bmin3_host, bmax3_host, res, brick, first, count, pts, stream);
+}
+
+extern "C" int gens_sparse_classify(const float* uc, int res, int brick, float t, float margin, uint8_t* flags, void* stream) {
+    return launch_classify("gens_sparse_classify", LATTICE_K28, uc, res, brick, t, margin, flags, stream);
+}
+
+extern "C" int gens_brick_active(const float* uc, int res, int brick, float t, float margin, uint8_t* flags, void* stream) {
+    return launch_classify("gens_brick_active", LATTICE_K29, uc, res, brick, t, margin, flags, stream);
 }
 
 extern "C" int gens_sparse_brick_points(const float* bmin3_host, const float* bmax3_host, int res, int brick, const int64_t* list, int64_t n_list,
                                         int64_t first, int64_t count, float* pts, void* stream) {
-    const char* who = "gens_sparse_brick_points";
-    if (int e = sparse_check(who, res, brick)) return e;
-    SparseBox b;
-    if (int e = sparse_box(who, bmin3_host, bmax3_host, b)) return e;
-    const SparseDims d = sparse_dims(res, brick);
-    int64_t rows = 0;
-    if (int e = sparse_rows(who, d, list, n_list, first, count, rows)) return e;
-    if (rows == 0) return 0;
-    GENS_CHECK_ARG(pts, GENS_EINVAL, "%s: null pointer (pts)", who);
-    brick_points_k<<<gens_blocks(rows, SPARSE_BLOCK), SPARSE_BLOCK, 0, (hipStream_t)stream>>>(b, d, list, (uint32_t)first, (uint32_t)rows, pts);
-    return gens_launch_status(who);
+    return launch_brick_points("gens_sparse_brick_points", LATTICE_K28, bmin3_host, bmax3_host, res, brick, list, n_list, first, count, pts, stream);
+}
+
+extern "C" int gens_brick_points(const float* bmin3_host, const float* bmax3_host, int res, int brick, const int64_t* list, int64_t n_list, int64_t first,
+                                 int64_t count, float* pts, void* stream) {
+    return launch_brick_points("gens_brick_points", LATTICE_K29, bmin3_host, bmax3_host, res, brick, list, n_list, first, count, pts, stream);
 }
 
 extern "C" int gens_sparse_fill(const float* uc, int res, int brick, float* u, void* stream) {
     const char* who = "gens_sparse_fill";
-    if (int e = sparse_check(who, res, brick)) return e;
+    if (int e = lattice_check(who, res, brick, LATTICE_K28)) return e;
     GENS_CHECK_ARG(uc && u, GENS_EINVAL, "%s: null pointer", who);
     GENS_CHECK_ARG(((uintptr_t)u & 15) == 0 && ((uintptr_t)uc & 3) == 0, GENS_EINVAL, "%s: misaligned pointer (u: 16 bytes; uc: 4 bytes)", who);
     const SparseDims d = sparse_dims(res, brick);
@@ -189,19 +194,18 @@ extern "C" int gens_sparse_fill(const float* uc, int res, int brick, float* u, v
 extern "C" int gens_sparse_scatter(const float* sdf, int res, int brick, const int64_t* list, int64_t n_list, int64_t first, int64_t count, float* u,
                                    void* stream) {
     const char* who = "gens_sparse_scatter";
-    if (int e = sparse_check(who, res, brick)) return e;
-    const SparseDims d = sparse_dims(res, brick);
-    int64_t rows = 0;
-    if (int e = sparse_rows(who, d, list, n_list, first, count, rows)) return e;
-    if (rows == 0) return 0;
+    if (int e = lattice_check(who, res, brick, LATTICE_K28)) return e;
+    if (int e = lattice_range(who, LATTICE_K28, brick, list, n_list, first, count, true)) return e;
+    if (count == 0) return 0;
     GENS_CHECK_ARG(sdf && u, GENS_EINVAL, "%s: null pointer", who);
-    scatter_k<<<gens_blocks(rows, SPARSE_BLOCK), SPARSE_BLOCK, 0, (hipStream_t)stream>>>(sdf, d, list, (uint32_t)first, (uint32_t)rows, u);
+    const int64_t rows = count * brick * brick * brick;
+    scatter_k<<<gens_blocks(rows, SPARSE_BLOCK), SPARSE_BLOCK, 0, (hipStream_t)stream>>>(sdf, sparse_dims(res, brick), list, (uint32_t)first, (uint32_t)rows, u);
     return gens_launch_status(who);
 }
 
 extern "C" int gens_sparse_leaks(const float* u, int res, int brick, const uint8_t* flags, float t, int64_t* leaks, void* stream) {
     const char* who = "gens_sparse_leaks";
-    if (int e = sparse_check(who, res, brick)) return e;
+    if (int e = lattice_check(who, res, brick, LATTICE_K28)) return e;
     GENS_CHECK_ARG(u && flags && leaks, GENS_EINVAL, "%s: null pointer", who);
     GENS_CHECK_ARG(((uintptr_t)leaks & 7) == 0 && ((uintptr_t)u & 3) == 0, GENS_EINVAL, "%s: misaligned pointer (u: 4 bytes; leaks: 8 bytes)", who);
     const SparseDims d = sparse_dims(res, brick);

@@ -1,81 +1,22 @@
-// K29: marching cubes on the bricks of the two-level lattice (K28's definitions: k28_sparse_lattice.hip) -- the
-// mesh of ops.marching_cubes(u_s, t), u_s the lattice ops.sparse_lattice would build, without u_s: device memory and work follow the
-// surface, and the limit is C^3 < 2^31 on the COARSE lattice instead of R^3 < 2^31.
-//   brick_coarse_points_k / brick_fine_points_k   K28's points under that limit (bit-equal to gens_lattice_points at the same per-axis index)
-//   brick_active_k                           K28's ACTIVE rule, one thread per deciding brick
+// K29: marching cubes on the bricks of the two-level lattice (its terms: k28_sparse_lattice.hip's header comment; its definitions and the
+// rules shared with K12 and K28: lattice.h) -- the mesh of ops.marching_cubes(u_s, t), u_s the lattice
+// ops.sparse_lattice would build, without u_s: device memory and work follow the surface, and the limit is C^3 < 2^31 on the COARSE
+// lattice instead of R^3 < 2^31.  The coarse points, the ACTIVE flags and the points of the listed bricks are K28's kernels under that limit
+// (gens_brick_coarse_points, gens_brick_active, gens_brick_points: k28_sparse_lattice.hip); here:
 //   brick_emit_flags_k                       a deciding brick EMITS if a brick of X + {0,1}^3 is active: every mixed-sign cell and every
 //                                            crossing edge of u_s starts at a point such a brick decides
 //   brick_mc_classify_k                      one workgroup per listed point brick: its (B + 1)^3 corner values staged in LDS (an evaluated
-//                                            point brick's stored value, else the fill from uc), then K12's decisions per point: vmask, case,
-//                                            the in-brick exclusive vertex rank; per brick the vertex, triangle and leak counts
-//   brick_mc_emit_k                          vertices (K12's float64 expression) at the brick's offset + rank, triangles through the slot map
+//                                            point brick's stored value, else the fill from uc), then K12's decisions per point (mc_decide):
+//                                            vmask, case, the in-brick exclusive vertex rank; per brick the vertex, triangle and leak counts
+//   brick_mc_emit_k                          vertices (K12's: mc_vertex) at the brick's offset + rank, triangles through the slot map
 //                                            of the listed bricks, one int64 sort key per vertex (3 flat(p) + axis) and triangle (flat(cell))
 // The listed unit is the POINT brick (B^3 points, fine index e * B + l per axis; an index past R - 1 is no point), so the plane R - 1 of
 // (R - 1) % B == 0 is a brick of its own here as in K28.  Per-axis indices and everything counted over the coarse or point-brick grids are
 // 32-bit; flat fine-lattice indices (the keys) are 64-bit.
-#include "common.h"
+#include "lattice.h"
 
 #define BRICK_POINTS_BLOCK 256
-#define BRICK_MAX 8
 #define BRICK_CORNERS ((BRICK_MAX + 1) * (BRICK_MAX + 1) * (BRICK_MAX + 1))
-
-// The checks every entry point shares; -> 0 or the error code.  All in 64 bits: res and brick are whatever the caller passed.
-static int brick_check(const char* who, int res, int brick) {
-    GENS_CHECK_ARG(res >= 2, GENS_EINVAL, "%s: res = %d, at least 2 points per axis", who, res);
-    GENS_CHECK_ARG(brick >= 2 && brick <= BRICK_MAX, GENS_EINVAL, "%s: brick = %d, 2 to %d cells", who, brick, BRICK_MAX);
-    const SparseDims d = sparse_dims(res, brick);
-    const int64_t lim = (int64_t)1 << 31;
-    GENS_CHECK_ARG((int64_t)d.coarse * d.coarse * d.coarse < lim && (int64_t)d.pbricks * d.pbricks * d.pbricks < lim, GENS_ELIMIT,
-                   "%s: res = %d, brick = %d: C^3 = %d^3 coarse points and P^3 = %d^3 point bricks must stay below 2^31", who, res, brick, d.coarse,
-                   d.pbricks);
-    return 0;
-}
-
-// The list range of the per-brick entry points -> 0 or the error code.  rows_per_brick > 0: the range is expanded to rows of 3 floats.
-static int brick_range(const char* who, const int64_t* list, int64_t n_list, int64_t first, int64_t count, int rows_per_brick) {
-    GENS_CHECK_ARG(n_list >= 0 && first >= 0 && count >= 0 && first <= n_list && count <= n_list - first, GENS_EINVAL,
-                   "%s: range [%lld, %lld + %lld) beyond the list of %lld bricks", who, (long long)first, (long long)first, (long long)count,
-                   (long long)n_list);
-    const int64_t lim = (int64_t)1 << 31;
-    GENS_CHECK_ARG(first < lim && count < lim && (rows_per_brick <= 0 || count < lim / 3 / rows_per_brick), GENS_ELIMIT,
-                   "%s: %lld bricks: fewer than 2^31 per call, and than 2^31 / 3 rows", who, (long long)count);
-    GENS_CHECK_ARG(count == 0 || list, GENS_EINVAL, "%s: null pointer (list)", who);
-    return 0;
-}
-
-__global__ __launch_bounds__(BRICK_POINTS_BLOCK) void brick_coarse_points_k(SparseBox b, SparseDims d, uint32_t first, uint32_t count, float* __restrict__ pts) {
-    const uint32_t t = blockIdx.x * BRICK_POINTS_BLOCK + threadIdx.x;
-    if (t >= count) return;
-    const uint32_t i = first + t, c = (uint32_t)d.coarse;
-    const uint32_t xy = i / c, kz = i - xy * c, ix = xy / c, jy = xy - ix * c;
-    const uint32_t last = (uint32_t)d.res - 1u;
-    float* p = pts + (size_t)3 * t;
-    p[0] = linspace_at(b.lo[0], b.hi[0], d.res, (int)min(ix * (uint32_t)d.brick, last));
-    p[1] = linspace_at(b.lo[1], b.hi[1], d.res, (int)min(jy * (uint32_t)d.brick, last));
-    p[2] = linspace_at(b.lo[2], b.hi[2], d.res, (int)min(kz * (uint32_t)d.brick, last));
-}
-
-__global__ __launch_bounds__(BRICK_POINTS_BLOCK) void brick_fine_points_k(SparseBox bx, SparseDims d, const int64_t* __restrict__ list, uint32_t first, uint32_t rows,
-                                                                     float* __restrict__ pts) {
-    const uint32_t t = blockIdx.x * BRICK_POINTS_BLOCK + threadIdx.x;
-    if (t >= rows) return;
-    int fx = 0, fy = 0, fz = 0;
-    (void)brick_row(d, list, first, t, fx, fy, fz);         // (a bad entry: the first lattice point; the caller's store never reads that row)
-    const int last = d.res - 1;
-    float* p = pts + (size_t)3 * t;
-    p[0] = linspace_at(bx.lo[0], bx.hi[0], d.res, min(fx, last));
-    p[1] = linspace_at(bx.lo[1], bx.hi[1], d.res, min(fy, last));
-    p[2] = linspace_at(bx.lo[2], bx.hi[2], d.res, min(fz, last));
-}
-
-__global__ __launch_bounds__(BRICK_POINTS_BLOCK) void brick_active_k(const float* __restrict__ uc, uint32_t c, float t, float margin, uint32_t n,
-                                                                     uint8_t* __restrict__ flags) {
-    const uint32_t i = blockIdx.x * BRICK_POINTS_BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t nb = c - 1u;
-    const uint32_t xy = i / nb, bz = i - xy * nb, bx = xy / nb, by = xy - bx * nb;
-    flags[i] = brick_is_active(uc, c, bx, by, bz, t, margin) ? 1 : 0;
-}
 
 __global__ __launch_bounds__(BRICK_POINTS_BLOCK) void brick_emit_flags_k(const uint8_t* __restrict__ active, uint32_t nb, uint32_t n, uint8_t* __restrict__ emit) {
     const uint32_t i = blockIdx.x * BRICK_POINTS_BLOCK + threadIdx.x;
@@ -176,31 +117,13 @@ __global__ __launch_bounds__(512) void brick_mc_classify_k(SparseDims d, BrickFi
         if (fx < r && fy < r && fz < r) {
             const uint32_t at = (lx * b1 + ly) * b1 + lz, sx = b1 * b1, sy = b1;
             const bool hx = fx + 1u < r, hy = fy + 1u < r, hz = fz + 1u < r;
-            // K12's decisions (mc_classify_k), corners in Bourke order
-            const bool b0 = s_u[at] < iso;
-            const bool c1 = hx ? s_u[at + sx] < iso : false;
-            const bool c3 = hy ? s_u[at + sy] < iso : false;
-            const bool c4 = hz ? s_u[at + 1u] < iso : false;
-            if (hx && c1 != b0) m |= 1u;
-            if (hy && c3 != b0) m |= 2u;
-            if (hz && c4 != b0) m |= 4u;
-            if (hx && hy && hz) {
-                const bool c2 = s_u[at + sx + sy] < iso, c5 = s_u[at + sx + 1u] < iso, c6 = s_u[at + sx + sy + 1u] < iso, c7 = s_u[at + sy + 1u] < iso;
-                cs = (b0 ? 1u : 0u) | (c1 ? 2u : 0u) | (c2 ? 4u : 0u) | (c3 ? 8u : 0u) | (c4 ? 16u : 0u) | (c5 ? 32u : 0u) | (c6 ? 64u : 0u) |
-                     (c7 ? 128u : 0u);
-                nt = tri_count[cs];
-            }
-            if (m) {                                        // K28's leak rule on the edges this point owns
-                const uint32_t nb = (uint32_t)d.coarse - 1u, lb = nb - 1u;
-                const bool own = f.active[(deciding_brick(fx, b, lb) * nb + deciding_brick(fy, b, lb)) * nb + deciding_brick(fz, b, lb)] != 0;
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    if (!(m & (1u << a))) continue;
-                    const uint32_t qx = fx + (a == 0), qy = fy + (a == 1), qz = fz + (a == 2);
-                    const bool other = f.active[(deciding_brick(qx, b, lb) * nb + deciding_brick(qy, b, lb)) * nb + deciding_brick(qz, b, lb)] != 0;
-                    if (!own || !other) ++leaks;
-                }
-            }
+            // corners in Bourke order; one that does not exist is not read
+            const bool b0 = s_u[at] < iso, c1 = hx ? s_u[at + sx] < iso : false, c3 = hy ? s_u[at + sy] < iso : false, c4 = hz ? s_u[at + 1u] < iso : false;
+            bool c2 = false, c5 = false, c6 = false, c7 = false;
+            if (hx && hy && hz) { c2 = s_u[at + sx + sy] < iso; c5 = s_u[at + sx + 1u] < iso; c6 = s_u[at + sx + sy + 1u] < iso; c7 = s_u[at + sy + 1u] < iso; }
+            m = mc_decide(b0, c1, c2, c3, c4, c5, c6, c7, hx, hy, hz, cs);
+            nt = tri_count[cs];                             // (case 0, no cell included: no triangle)
+            if (m) leaks = leaking_edges(f.active, d, fx, fy, fz, m);
         }
         vmask[at0 + l] = (uint8_t)m;
         cases[at0 + l] = (uint8_t)cs;
@@ -242,17 +165,12 @@ __global__ __launch_bounds__(512) void brick_mc_emit_k(SparseDims d, BrickField 
     if (m) {
         const uint32_t at = (lx * b1 + ly) * b1 + lz;
         const uint32_t step[3] = {b1 * b1, b1, 1u};
-        const double a = (double)s_u[at], lvl = (double)iso;
+        const float a = s_u[at];
         int64_t o = voff[blockIdx.x] + rank[at0 + l];
 #pragma unroll
         for (int ax = 0; ax < 3; ++ax) {
             if (!(m & (1u << ax))) continue;
-            const double q = (double)s_u[at + step[ax]];
-            const double t = (lvl - a) / (q - a);           // K12's expression (mc_emit_k)
-            double* v = vertices + 3 * o;
-            v[0] = (double)fx + (ax == 0 ? t : 0.0);
-            v[1] = (double)fy + (ax == 1 ? t : 0.0);
-            v[2] = (double)fz + (ax == 2 ? t : 0.0);
+            mc_vertex(vertices + 3 * o, (double)fx, (double)fy, (double)fz, ax, a, s_u[at + step[ax]], iso);
             vkey[o] = 3 * flat + ax;
             ++o;
         }
@@ -264,14 +182,13 @@ __global__ __launch_bounds__(512) void brick_mc_emit_k(SparseDims d, BrickField 
         for (uint32_t t = 0; t < 3u * nt; ++t) {
             const int e = row[t];
             const uint32_t cx = lx + (uint32_t)c_edge_owner[e][0], cy = ly + (uint32_t)c_edge_owner[e][1], cz = lz + (uint32_t)c_edge_owner[e][2];
-            const uint32_t below = (1u << c_edge_owner[e][3]) - 1u;
             // the owner's point brick (the cell exists, so every index is <= R - 1 and the brick <= P - 1) and its place in it
             const uint32_t qx = ex + (cx == b), qy = ey + (cy == b), qz = ez + (cz == b);
             const int32_t slot = eslot[(qx * p + qy) * p + qz];
             int32_t id = -1;                                // an owner in no listed brick: cannot be; never an index out of range
             if (slot >= 0) {
                 const size_t q = (size_t)slot * b3 + ((cx == b ? 0u : cx) * b + (cy == b ? 0u : cy)) * b + (cz == b ? 0u : cz);
-                id = (int32_t)(voff[slot] + rank[q] + (int64_t)__popc((uint32_t)vmask[q] & below));
+                id = (int32_t)mc_vertex_id(voff[slot] + (int64_t)rank[q], vmask[q], e);
             }
             out[t] = id;
         }
@@ -279,52 +196,9 @@ __global__ __launch_bounds__(512) void brick_mc_emit_k(SparseDims d, BrickField 
     }
 }
 
-extern "C" int gens_brick_coarse_points(const float* bmin3_host, const float* bmax3_host, int res, int brick, int64_t first, int64_t count,
-                                        float* pts, void* stream) {
-    const char* who = "gens_brick_coarse_points";
-    if (int e = brick_check(who, res, brick)) return e;
-    SparseBox b;
-    if (int e = sparse_box(who, bmin3_host, bmax3_host, b)) return e;
-    const SparseDims d = sparse_dims(res, brick);
-    const int64_t n = (int64_t)d.coarse * d.coarse * d.coarse;
-    GENS_CHECK_ARG(first >= 0 && count >= 0 && first <= n && count <= n - first, GENS_EINVAL, "%s: range [%lld, %lld + %lld) beyond the %d^3 coarse points",
-                   who, (long long)first, (long long)first, (long long)count, d.coarse);
-    GENS_CHECK_ARG(count < ((int64_t)1 << 31) / 3, GENS_ELIMIT, "%s: %lld points: fewer than 2^31 / 3 per call", who, (long long)count);
-    if (count == 0) return 0;
-    GENS_CHECK_ARG(pts, GENS_EINVAL, "%s: null pointer (pts)", who);
-    brick_coarse_points_k<<<gens_blocks(count, BRICK_POINTS_BLOCK), BRICK_POINTS_BLOCK, 0, (hipStream_t)stream>>>(b, d, (uint32_t)first, (uint32_t)count, pts);
-    return gens_launch_status(who);
-}
-
-extern "C" int gens_brick_points(const float* bmin3_host, const float* bmax3_host, int res, int brick, const int64_t* list, int64_t n_list,
-                                 int64_t first, int64_t count, float* pts, void* stream) {
-    const char* who = "gens_brick_points";
-    if (int e = brick_check(who, res, brick)) return e;
-    SparseBox b;
-    if (int e = sparse_box(who, bmin3_host, bmax3_host, b)) return e;
-    if (int e = brick_range(who, list, n_list, first, count, brick * brick * brick)) return e;
-    if (count == 0) return 0;
-    GENS_CHECK_ARG(pts, GENS_EINVAL, "%s: null pointer (pts)", who);
-    const SparseDims d = sparse_dims(res, brick);
-    const int64_t rows = count * brick * brick * brick;
-    brick_fine_points_k<<<gens_blocks(rows, BRICK_POINTS_BLOCK), BRICK_POINTS_BLOCK, 0, (hipStream_t)stream>>>(b, d, list, (uint32_t)first, (uint32_t)rows, pts);
-    return gens_launch_status(who);
-}
-
-extern "C" int gens_brick_active(const float* uc, int res, int brick, float t, float margin, uint8_t* flags, void* stream) {
-    const char* who = "gens_brick_active";
-    if (int e = brick_check(who, res, brick)) return e;
-    GENS_CHECK_ARG(uc && flags, GENS_EINVAL, "%s: null pointer", who);
-    GENS_CHECK_ARG(margin >= 0.0f, GENS_EINVAL, "%s: margin = %g, must be >= 0 (and no NaN)", who, (double)margin);
-    const SparseDims d = sparse_dims(res, brick);
-    const int64_t n = (int64_t)(d.coarse - 1) * (d.coarse - 1) * (d.coarse - 1);
-    brick_active_k<<<gens_blocks(n, BRICK_POINTS_BLOCK), BRICK_POINTS_BLOCK, 0, (hipStream_t)stream>>>(uc, (uint32_t)d.coarse, t, margin, (uint32_t)n, flags);
-    return gens_launch_status(who);
-}
-
 extern "C" int gens_brick_emit_flags(const uint8_t* active, int res, int brick, uint8_t* emit, void* stream) {
     const char* who = "gens_brick_emit_flags";
-    if (int e = brick_check(who, res, brick)) return e;
+    if (int e = lattice_check(who, res, brick, LATTICE_K29)) return e;
     GENS_CHECK_ARG(active && emit, GENS_EINVAL, "%s: null pointer", who);
     const SparseDims d = sparse_dims(res, brick);
     const int64_t n = (int64_t)(d.coarse - 1) * (d.coarse - 1) * (d.coarse - 1);
@@ -339,8 +213,8 @@ extern "C" int gens_brick_mc_classify(const float* uc, const float* store, const
                                       const int64_t* list, int64_t n_list, float iso, const uint8_t* tri_count, uint8_t* vmask, uint8_t* cases,
                                       uint16_t* rank, int32_t* counts, void* stream) {
     const char* who = "gens_brick_mc_classify";
-    if (int e = brick_check(who, res, brick)) return e;
-    if (int e = brick_range(who, list, n_list, 0, n_list, 0)) return e;
+    if (int e = lattice_check(who, res, brick, LATTICE_K29)) return e;
+    if (int e = lattice_range(who, LATTICE_K29, brick, list, n_list, 0, n_list, false)) return e;
     if (n_list == 0) return 0;
     GENS_CHECK_ARG(uc && store && pslot && active && tri_count && vmask && cases && rank && counts, GENS_EINVAL, "%s: null pointer", who);
     GENS_CHECK_ARG(((uintptr_t)rank & 1) == 0 && ((uintptr_t)counts & 3) == 0 && ((uintptr_t)pslot & 3) == 0, GENS_EINVAL,
@@ -356,8 +230,8 @@ extern "C" int gens_brick_mc_emit(const float* uc, const float* store, const int
                                   const uint8_t* vmask, const uint8_t* cases, const uint16_t* rank, const int64_t* voff, const int64_t* toff,
                                   double* vertices, int32_t* triangles, int64_t* vkey, int64_t* tkey, void* stream) {
     const char* who = "gens_brick_mc_emit";
-    if (int e = brick_check(who, res, brick)) return e;
-    if (int e = brick_range(who, list, n_list, 0, n_list, 0)) return e;
+    if (int e = lattice_check(who, res, brick, LATTICE_K29)) return e;
+    if (int e = lattice_range(who, LATTICE_K29, brick, list, n_list, 0, n_list, false)) return e;
     GENS_CHECK_ARG(table_stride >= 15, GENS_EINVAL, "%s: table stride %d", who, table_stride);
     if (n_list == 0) return 0;
     GENS_CHECK_ARG(uc && store && pslot && eslot && tri_table && tri_count && vmask && cases && rank && voff && toff && vertices && triangles && vkey && tkey,

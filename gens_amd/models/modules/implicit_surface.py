@@ -576,22 +576,36 @@ class ImplicitSurface(nn.Module):
     sparse_mesh = None             # True: extract_geometry runs marching cubes on the sparse lattice's bricks (ops.brick_marching_cubes, K29) and
                                    # builds no dense lattice; needs a sparse brick of 2 to 8 cells.  None / False: off
 
-    def _lattice_brick(self, sparse, shard):
-        """The brick edge of this call, or None for the dense lattice.  sparse: None = the attribute `sparse_lattice`, False = dense."""
-        if sparse is None:
-            sparse = self.sparse_lattice
-        if sparse is None or sparse is False:
-            return None
+    def _lattice_route(self, sparse, sparse_mesh, shard):
+        """The options of sdf_grid (sparse_mesh=False) and extract_geometry -> (route, brick edge): "dense" (the dense lattice, brick None),
+        "lattice" (ops.sparse_lattice, K28) or "mesh" (ops.brick_marching_cubes, K29).  None = the attribute of that name; sparse False =
+        dense, True = SPARSE_BRICK.  With a shard neither option is in effect: one warning each, and the brick limit of K29 is not looked at."""
+        def unsharded(once, what):                     # -> the route with a shard
+            if not getattr(self, once, False):
+                import warnings
+                warnings.warn(f"gens_amd: {what}", RuntimeWarning, stacklevel=4)
+                setattr(self, once, True)
+            return "dense", None
+
+        sparse = self.sparse_lattice if sparse is None else sparse
+        sparse_mesh = self.sparse_mesh if sparse_mesh is None else sparse_mesh
+        off = sparse is None or sparse is False
+        if sparse_mesh and off:
+            raise ValueError("sparse_mesh needs the sparse lattice: pass sparse (a brick edge of 2 to 8 cells, or True) or set `sparse_lattice`")
+        if off:
+            return "dense", None
+        if sparse_mesh and shard is not None:          # (before the brick is looked at: with a shard the option is not in effect)
+            return unsharded("_warned_sparse_mesh_shard", "sparse_mesh is not sharded: with a shard the lattice is gathered and marching cubes runs on it")
         brick = self.SPARSE_BRICK if sparse is True else int(sparse)
+        if sparse_mesh:
+            if not 2 <= brick <= ops.BRICK_MC_MAX:
+                raise ValueError(f"sparse_mesh: sparse = {sparse!r}, the brick-sparse marching cubes takes bricks of 2 to {ops.BRICK_MC_MAX} cells")
+            return "mesh", brick
         if brick < 1:
             raise ValueError(f"sparse = {sparse!r}: the brick edge in cells, at least 1 (or True / None)")
         if shard is not None:
-            if not getattr(self, "_warned_sparse_shard", False):
-                import warnings
-                warnings.warn("gens_amd: the sparse lattice is not sharded: with a shard the dense lattice is evaluated", RuntimeWarning, stacklevel=3)
-                self._warned_sparse_shard = True
-            return None
-        return brick
+            return unsharded("_warned_sparse_shard", "the sparse lattice is not sharded: with a shard the dense lattice is evaluated")
+        return "lattice", brick
 
     def _lattice_passes(self, vols, shard, run):
         """run(evaluate) with the lattice's evaluator (the fused plan and this scene's precision, else the PyTorch layers) -> its result.  A
@@ -624,7 +638,7 @@ class ImplicitSurface(nn.Module):
         total = resolution ** 3
         n_chunks = -(-total // chunk)
         own = range(n_chunks) if shard is None else shard.chunks(n_chunks)
-        brick = self._lattice_brick(sparse, shard)
+        brick = self._lattice_route(sparse, False, shard)[1]
         self.last_lattice_stats = None
         if brick is None:
             u = torch.zeros(len(own), chunk, device=dev) if shard is not None else torch.empty(total, device=dev)
@@ -653,28 +667,6 @@ class ImplicitSurface(nn.Module):
             u = u.reshape(-1)[:total]
         return u.reshape(resolution, resolution, resolution)
 
-    def _mesh_brick(self, sparse, sparse_mesh, shard):
-        """The brick edge of a brick-sparse extraction (K29), or None for the lattice route.  sparse_mesh: None = the attribute."""
-        if sparse_mesh is None:
-            sparse_mesh = self.sparse_mesh
-        if not sparse_mesh:
-            return None
-        if sparse is None:
-            sparse = self.sparse_lattice
-        if sparse is None or sparse is False:
-            raise ValueError("sparse_mesh needs the sparse lattice: pass sparse (a brick edge of 2 to 8 cells, or True) or set `sparse_lattice`")
-        if shard is not None:                          # (before the brick is looked at: with a shard the option is not in effect)
-            if not getattr(self, "_warned_sparse_mesh_shard", False):
-                import warnings
-                warnings.warn("gens_amd: sparse_mesh is not sharded: with a shard the lattice is gathered and marching cubes runs on it",
-                              RuntimeWarning, stacklevel=3)
-                self._warned_sparse_mesh_shard = True
-            return None
-        brick = self.SPARSE_BRICK if sparse is True else int(sparse)
-        if not 2 <= brick <= ops.BRICK_MC_MAX:
-            raise ValueError(f"sparse_mesh: sparse = {sparse!r}, the brick-sparse marching cubes takes bricks of 2 to {ops.BRICK_MC_MAX} cells")
-        return brick
-
     @torch.no_grad()
     def _brick_mesh(self, volumes, bound_min, bound_max, resolution, threshold, brick):
         """Vertices (index coordinates) and triangles on the device through ops.brick_marching_cubes; None if the leak count refutes the bound
@@ -689,9 +681,8 @@ class ImplicitSurface(nn.Module):
         if not stats["leaks"]:
             return vertices, triangles
         dense_fits = resolution ** 3 < 1 << 31
-        warnings.warn(f"sparse_mesh: {stats['leaks']} lattice edges cross the threshold {float(threshold)!r} next to an inactive brick, so the field "
-                      f"is not {float(self.lattice_lipschitz)!r}-Lipschitz on this lattice (resolution {resolution}, brick {brick}); "
-                      + ("extracting from the dense lattice instead" if dense_fits else "there is no dense lattice at this resolution"),
+        then = "extracting from the dense lattice instead" if dense_fits else "there is no dense lattice at this resolution"
+        warnings.warn(ops.lattice_leak_message("sparse_mesh", stats["leaks"], threshold, self.lattice_lipschitz, resolution, brick, then),
                       RuntimeWarning, stacklevel=4)
         if not dense_fits:
             raise RuntimeError(f"sparse_mesh: {stats['leaks']} leaks at resolution {resolution}: the mesh would have holes, and {resolution}^3 points "
@@ -705,9 +696,9 @@ class ImplicitSurface(nn.Module):
         together with a sparse brick of 2 to 8 cells, marching cubes runs on the bricks (ops.brick_marching_cubes) and no dense lattice is
         built -- the same mesh, resolutions beyond 1290 included.  A leak count above zero warns and takes the dense lattice (RuntimeError
         where resolution^3 >= 2^31 leaves none); with a shard the option is ignored with one warning."""
-        brick = self._mesh_brick(sparse, sparse_mesh, shard)
+        route, brick = self._lattice_route(sparse, sparse_mesh, shard)
         mesh = None
-        if brick is not None:
+        if route == "mesh":
             mesh = self._brick_mesh(volumes, bound_min, bound_max, resolution, threshold, brick)
             if mesh is None:                           # the bound failed: the dense lattice, evaluated once
                 stats = self.last_lattice_stats

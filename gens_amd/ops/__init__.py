@@ -21,7 +21,8 @@ is what it was when ops was one module:
     ops.finalize  K25: elliptical dilation and vertex mask votes of the DTU mesh finalising (evaluation/clean_meshes.py).
     ops.filter    K26: the mask pyramid restricted to the dilated SDF band (GenS.filter_volume, models/gens.py:87-122);
                   K27: the largest connected region of a mask volume (clean_volume, utils/tools.py:34-50).
-    ops.lattice   K28: the two-level SDF lattice of extract_geometry, evaluated near the iso-surface only (sparse_lattice).
+    ops.lattice   K28: the two-level SDF lattice of extract_geometry, evaluated near the iso-surface only (sparse_lattice), and what K29
+                  shares with it: dimensions, point and classify launches under either set of limits, the front end of both.
     ops.brick_mcubes  K29: marching cubes on that lattice's bricks, without the dense lattice (brick_marching_cubes).
 """
 from .base import *  # noqa: F401,F403

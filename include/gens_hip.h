@@ -877,6 +877,8 @@ int gens_sparse_leaks(const float* u, int res, int brick, const uint8_t* flags, 
  *     gens_brick_coarse_points / gens_brick_points: gens_sparse_coarse_points / gens_sparse_brick_points under these limits, bit-equal to
  *       gens_lattice_points at the same per-axis index; count < 2^31 / 3 rows per call.
  *     gens_brick_active: gens_sparse_classify's rule: uc (C^3) -> flags ((C - 1)^3) bytes.
+ *     (These three launch K28's kernels, csrc/k28_sparse_lattice.hip; the rest is csrc/k29_brick_mcubes.hip.  The limits of both families
+ *     and every rule K12, K28 and K29 share are written once, in csrc/lattice.h.)
  *     gens_brick_emit_flags: emit[X] = 1 if a brick of X + {0,1}^3 (clipped to the (C - 1)^3 grid) is active.  Every cell of K28's lattice
  *       with corners on both sides of t, and every crossing edge, starts at a point decided by such a brick.
  *   The per-brick calls take `list`: n_list (< 2^31) int64 point-brick numbers on the DEVICE, the point bricks whose deciding brick emits

@@ -14,7 +14,6 @@ from . import sparse_lattice_reference as SR
 gpu = pytest.mark.gpu
 
 LO, HI = (-1.0, -1.0, -1.0), (1.0, 1.0, 1.0)
-BOX_LO, BOX_HI = (-1.0, -0.9, -1.1), (1.0, 1.05, 0.95)          # an uneven box for the point kernels: every axis has its own spacing
 K29 = {"gens_brick_coarse_points", "gens_brick_points", "gens_brick_active", "gens_brick_emit_flags", "gens_brick_mc_classify", "gens_brick_mc_emit"}
 
 
@@ -28,23 +27,8 @@ def _bits(t):
 @gpu
 @pytest.mark.parametrize("r,b", [(r, b) for r in (9, 10, 33, 100) for b in (4, 8)])
 def test_coarse_and_brick_points_are_the_lattice_points_bit_for_bit(r, b):
-    from gens_amd import ops
-    dev = torch.device("cuda")
-    full = ops.lattice_points(BOX_LO, BOX_HI, r, 0, r ** 3, dev).cpu().reshape(r, r, r, 3)
-    c, _, p = SR.dims(r, b)
-    assert ops.brick_mc_dims(r, b) == (c, p)
-    ci = SR.coarse_index(r, b)
-    want = full[ci][:, ci][:, :, ci].reshape(-1, 3)
-    assert torch.equal(_bits(ops.brick_coarse_points(BOX_LO, BOX_HI, r, b, 0, c ** 3, dev)), _bits(want))
-    first, count = c ** 3 // 3, c ** 3 - c ** 3 // 3 - 1                                   # a range that starts and ends inside a row
-    assert torch.equal(_bits(ops.brick_coarse_points(BOX_LO, BOX_HI, r, b, first, count, dev)), _bits(want[first:first + count]))
-    entries = torch.randperm(p ** 3, generator=torch.Generator().manual_seed(r * 16 + b))
-    rows = SR.brick_rows(r, b, entries).clamp(max=r - 1)
-    want = full[rows[:, 0], rows[:, 1], rows[:, 2]]
-    got = ops.brick_points(BOX_LO, BOX_HI, r, b, entries.cuda(), 0, len(entries))
-    assert got.shape == (len(entries) * b ** 3, 3) and torch.equal(_bits(got), _bits(want))
-    first, count = len(entries) // 2, len(entries) - len(entries) // 2
-    assert torch.equal(_bits(ops.brick_points(BOX_LO, BOX_HI, r, b, entries.cuda(), first, count)), _bits(want[first * b ** 3:]))
+    from .test_hip_sparse_lattice import check_points_are_the_lattice_points_bit_for_bit
+    check_points_are_the_lattice_points_bit_for_bit("brick", r, b)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------
@@ -365,6 +349,7 @@ def test_validate_passes_the_option_through(golden):
 def test_entry_points_report_bad_arguments_without_a_gpu():
     import ctypes as C
     from gens_amd import lib as L
+    from .test_hip_sparse_lattice import check_shared_refusals
     lib = L.load()
     lo, hi = (C.c_float * 3)(-1, -1, -1), (C.c_float * 3)(1, 1, 1)
     one = C.c_void_p(16)                                                  # a non-null, aligned pointer: every call below is refused before it is used
@@ -384,19 +369,8 @@ def test_entry_points_report_bad_arguments_without_a_gpu():
             assert call(64, b) == -1 and b"brick = %d" % b in lib.gens_last_error()
         assert call(10400, 8) == -2 and b"2^31" in lib.gens_last_error()               # C = 1301: 1301^3 >= 2^31 > 1290^3
         assert call(5161, 4) == -2                                                      # C = 1291 at the other brick
-    assert lib.gens_brick_coarse_points(None, hi, 16, 4, 0, 1, one, None) == -1 and b"null" in lib.gens_last_error()
-    assert lib.gens_brick_coarse_points(lo, hi, 16, 4, 0, 1, None, None) == -1 and b"null" in lib.gens_last_error()
-    assert lib.gens_brick_coarse_points(lo, hi, 16, 4, 100, 26, one, None) == -1 and b"beyond" in lib.gens_last_error()       # C = 5: 125 points
-    assert lib.gens_brick_coarse_points(lo, hi, 16, 4, -1, 1, one, None) == -1
-    assert lib.gens_brick_coarse_points(lo, hi, 16, 4, 125, 0, None, None) == 0                                              # an empty range asks for nothing
-    assert lib.gens_brick_points(lo, hi, 16, 4, one, 3, 2, 2, one, None) == -1 and b"beyond the list" in lib.gens_last_error()
-    assert lib.gens_brick_points(lo, hi, 16, 4, None, 3, 0, 3, one, None) == -1 and b"null" in lib.gens_last_error()
-    assert lib.gens_brick_points(lo, hi, 16, 4, one, 3, 0, 3, None, None) == -1 and b"null" in lib.gens_last_error()
+    check_shared_refusals(lib, "gens_brick_coarse_points", "gens_brick_active", "gens_brick_points")
     assert lib.gens_brick_points(lo, hi, 4096, 8, one, 1 << 24, 0, 1 << 24, one, None) == -2 and b"rows" in lib.gens_last_error()   # 2^24 * 512 rows
-    assert lib.gens_brick_points(lo, hi, 16, 4, None, 0, 0, 0, None, None) == 0
-    assert lib.gens_brick_active(None, 16, 4, 0.0, 0.1, one, None) == -1 and b"null" in lib.gens_last_error()
-    assert lib.gens_brick_active(one, 16, 4, 0.0, -0.1, one, None) == -1 and b"margin" in lib.gens_last_error()
-    assert lib.gens_brick_active(one, 16, 4, 0.0, float("nan"), one, None) == -1
     assert lib.gens_brick_emit_flags(None, 16, 4, one, None) == -1 and b"null" in lib.gens_last_error()
     assert lib.gens_brick_emit_flags(one, 16, 4, None, None) == -1
     assert lib.gens_brick_mc_classify(one, one, one, one, 16, 4, one, -1, 0.0, one, one, one, one, one, None) == -1

@@ -14,6 +14,9 @@ gpu = pytest.mark.gpu
 LO, HI = (-1.0, -1.0, -1.0), (1.0, 1.0, 1.0)
 BOX_LO, BOX_HI = (-1.0, -0.9, -1.1), (1.0, 1.05, 0.95)          # an uneven box for the point kernels: every axis has its own spacing
 SIZES = [(9, 4), (9, 8), (10, 4), (10, 8), (33, 4), (33, 8), (100, 4), (100, 8)]
+# the operators both families of entry points have (K28's gens_sparse_*, K29's gens_brick_*): dims, coarse points, brick points, classify
+FAMILIES = {"sparse": ("sparse_lattice_dims", "sparse_coarse_points", "sparse_brick_points", "sparse_classify"),
+            "brick": ("brick_mc_dims", "brick_coarse_points", "brick_points", "brick_active")}
 K28 = {"gens_sparse_coarse_points", "gens_sparse_classify", "gens_sparse_brick_points", "gens_sparse_fill", "gens_sparse_scatter",
        "gens_sparse_leaks"}
 
@@ -25,28 +28,35 @@ def _bits(t):
 # ------------------------------------------------------------------------------------------------------------------------------------
 # the kernels, one by one
 # ------------------------------------------------------------------------------------------------------------------------------------
-@gpu
-@pytest.mark.parametrize("r,b", SIZES)
-def test_coarse_and_brick_points_are_the_lattice_points_bit_for_bit(r, b):
+def check_points_are_the_lattice_points_bit_for_bit(family, r, b):
+    """A family's coarse and brick points against gens_lattice_points (tests/test_hip_brick_mcubes.py runs it for K29's)."""
     from gens_amd import ops
+    dims, coarse_points, brick_points = (getattr(ops, n) for n in FAMILIES[family][:3])
     dev = torch.device("cuda")
     full = ops.lattice_points(BOX_LO, BOX_HI, r, 0, r ** 3, dev).cpu().reshape(r, r, r, 3)
     c, _, p = SR.dims(r, b)
+    assert dims(r, b) == (c, p)
     ci = SR.coarse_index(r, b)
     want = full[ci][:, ci][:, :, ci].reshape(-1, 3)
-    got = ops.sparse_coarse_points(BOX_LO, BOX_HI, r, b, 0, c ** 3, dev).cpu()
+    got = coarse_points(BOX_LO, BOX_HI, r, b, 0, c ** 3, dev).cpu()
     assert torch.equal(_bits(got), _bits(want))
     first, count = c ** 3 // 3, c ** 3 - c ** 3 // 3 - 1                                   # a range that starts and ends inside a row
-    assert torch.equal(_bits(ops.sparse_coarse_points(BOX_LO, BOX_HI, r, b, first, count, dev)), _bits(want[first:first + count]))
+    assert torch.equal(_bits(coarse_points(BOX_LO, BOX_HI, r, b, first, count, dev)), _bits(want[first:first + count]))
     g = torch.Generator().manual_seed(r * 16 + b)
     entries = torch.randperm(p ** 3, generator=g)
     rows = SR.brick_rows(r, b, entries).clamp(max=r - 1)
     want = full[rows[:, 0], rows[:, 1], rows[:, 2]]
-    got = ops.sparse_brick_points(BOX_LO, BOX_HI, r, b, entries.cuda(), 0, len(entries))
+    got = brick_points(BOX_LO, BOX_HI, r, b, entries.cuda(), 0, len(entries))
     assert got.shape == (len(entries) * b ** 3, 3) and torch.equal(_bits(got), _bits(want))
     first, count = len(entries) // 2, len(entries) - len(entries) // 2
-    got = ops.sparse_brick_points(BOX_LO, BOX_HI, r, b, entries.cuda(), first, count)
+    got = brick_points(BOX_LO, BOX_HI, r, b, entries.cuda(), first, count)
     assert torch.equal(_bits(got), _bits(want[first * b ** 3:]))
+
+
+@gpu
+@pytest.mark.parametrize("r,b", SIZES)
+def test_coarse_and_brick_points_are_the_lattice_points_bit_for_bit(r, b):
+    check_points_are_the_lattice_points_bit_for_bit("sparse", r, b)
 
 
 def _planted_corners(c, t, mrg, seed):
@@ -67,6 +77,8 @@ def _planted_corners(c, t, mrg, seed):
 @gpu
 @pytest.mark.parametrize("r,b", SIZES)
 def test_classify_equals_the_active_rule(r, b):
+    """Both families' classify: SIZES has 2 <= B <= 8 throughout, K29's limit, with the plane brick (R = 9: P == C) and the ragged last brick
+    (R = 10)."""
     from gens_amd import ops
     c, nb, _ = SR.dims(r, b)
     seen = set()
@@ -75,9 +87,10 @@ def test_classify_equals_the_active_rule(r, b):
             for seed in range(3 if c <= 4 else 1):            # (few corners: more draws, so that every planted value is met somewhere)
                 uc = _planted_corners(c, t, mrg, 7 * r + b + seed)
                 want = SR.active(uc, t, mrg)
-                got = ops.sparse_classify(uc.cuda(), r, b, t, mrg).cpu().reshape(nb, nb, nb)
-                assert torch.equal(got.bool(), want), (t, mrg)
-                assert set(got.unique().tolist()) <= {0, 1}
+                for family in sorted(FAMILIES):
+                    got = getattr(ops, FAMILIES[family][3])(uc.cuda(), r, b, t, mrg).cpu().reshape(nb, nb, nb)
+                    assert torch.equal(got.bool(), want), (family, t, mrg)
+                    assert set(got.unique().tolist()) <= {0, 1}
                 seen |= set(want.reshape(-1).tolist())
     if nb > 2:
         assert seen == {False, True}                                   # both answers occur: the comparison above is not vacuous
@@ -404,6 +417,27 @@ def test_validate_passes_the_option_through(golden):
 # ------------------------------------------------------------------------------------------------------------------------------------
 # argument checks: before any launch, so they run without a device
 # ------------------------------------------------------------------------------------------------------------------------------------
+def check_shared_refusals(lib, coarse_points, classify, brick_points):
+    """What the coarse-point, classify and brick-point entry points of either family refuse alike (tests/test_hip_brick_mcubes.py runs it
+    for K29's)."""
+    import ctypes as C
+    coarse_points, classify, brick_points = (getattr(lib, n) for n in (coarse_points, classify, brick_points))
+    lo, hi = (C.c_float * 3)(-1, -1, -1), (C.c_float * 3)(1, 1, 1)
+    one = C.c_void_p(16)
+    assert coarse_points(None, hi, 16, 4, 0, 1, one, None) == -1 and b"null" in lib.gens_last_error()
+    assert coarse_points(lo, hi, 16, 4, 0, 1, None, None) == -1 and b"null" in lib.gens_last_error()
+    assert coarse_points(lo, hi, 16, 4, 100, 26, one, None) == -1 and b"beyond" in lib.gens_last_error()      # C = 5: 125 points
+    assert coarse_points(lo, hi, 16, 4, -1, 1, one, None) == -1
+    assert coarse_points(lo, hi, 16, 4, 125, 0, None, None) == 0                                             # an empty range asks for nothing
+    assert classify(None, 16, 4, 0.0, 0.1, one, None) == -1 and b"null" in lib.gens_last_error()
+    assert classify(one, 16, 4, 0.0, -0.1, one, None) == -1 and b"margin" in lib.gens_last_error()
+    assert classify(one, 16, 4, 0.0, float("nan"), one, None) == -1
+    assert brick_points(lo, hi, 16, 4, one, 3, 2, 2, one, None) == -1 and b"beyond the list" in lib.gens_last_error()
+    assert brick_points(lo, hi, 16, 4, None, 3, 0, 3, one, None) == -1 and b"null" in lib.gens_last_error()
+    assert brick_points(lo, hi, 16, 4, one, 3, 0, 3, None, None) == -1 and b"null" in lib.gens_last_error()
+    assert brick_points(lo, hi, 16, 4, None, 0, 0, 0, None, None) == 0
+
+
 def test_entry_points_report_bad_arguments_without_a_gpu():
     import ctypes as C
     from gens_amd import lib as L
@@ -424,20 +458,9 @@ def test_entry_points_report_bad_arguments_without_a_gpu():
         assert call(1, 4) == -1 and b"res = 1" in lib.gens_last_error() and name.encode() in lib.gens_last_error()
         assert call(16, 0) == -1 and b"brick = 0" in lib.gens_last_error()
         assert call(1291, 4) == -2 and b"2^31" in lib.gens_last_error()               # 1291^3 >= 2^31 > 1290^3
-    assert lib.gens_sparse_coarse_points(None, hi, 16, 4, 0, 1, one, None) == -1 and b"null" in lib.gens_last_error()
-    assert lib.gens_sparse_coarse_points(lo, hi, 16, 4, 0, 1, None, None) == -1 and b"null" in lib.gens_last_error()
-    assert lib.gens_sparse_coarse_points(lo, hi, 16, 4, 100, 26, one, None) == -1 and b"beyond" in lib.gens_last_error()      # C = 5: 125 points
-    assert lib.gens_sparse_coarse_points(lo, hi, 16, 4, -1, 1, one, None) == -1
-    assert lib.gens_sparse_coarse_points(lo, hi, 16, 4, 125, 0, None, None) == 0                                             # an empty range asks for nothing
-    assert lib.gens_sparse_classify(None, 16, 4, 0.0, 0.1, one, None) == -1 and b"null" in lib.gens_last_error()
-    assert lib.gens_sparse_classify(one, 16, 4, 0.0, -0.1, one, None) == -1 and b"margin" in lib.gens_last_error()
-    assert lib.gens_sparse_classify(one, 16, 4, 0.0, float("nan"), one, None) == -1
-    assert lib.gens_sparse_brick_points(lo, hi, 16, 4, one, 3, 2, 2, one, None) == -1 and b"beyond the list" in lib.gens_last_error()
-    assert lib.gens_sparse_brick_points(lo, hi, 16, 4, None, 3, 0, 3, one, None) == -1 and b"null" in lib.gens_last_error()
-    assert lib.gens_sparse_brick_points(lo, hi, 16, 4, one, 3, 0, 3, None, None) == -1 and b"null" in lib.gens_last_error()
+    check_shared_refusals(lib, "gens_sparse_coarse_points", "gens_sparse_classify", "gens_sparse_brick_points")
     assert lib.gens_sparse_brick_points(lo, hi, 1200, 1025, one, 3, 0, 1, one, None) == -2
     assert lib.gens_sparse_brick_points(lo, hi, 1024, 512, one, 8, 0, 8, one, None) == -2 and b"rows" in lib.gens_last_error()   # 8 * 512^3 rows
-    assert lib.gens_sparse_brick_points(lo, hi, 16, 4, None, 0, 0, 0, None, None) == 0
     assert lib.gens_sparse_fill(one, 16, 4, C.c_void_p(20), None) == -1 and b"misaligned" in lib.gens_last_error()
     assert lib.gens_sparse_fill(None, 16, 4, one, None) == -1
     assert lib.gens_sparse_scatter(one, 16, 4, one, 3, 0, 4, one, None) == -1 and b"beyond the list" in lib.gens_last_error()
