@@ -23,15 +23,47 @@ def transform_vertices(vertices, matrix):
     return v @ m[:3, :3].T + m[:3, 3]
 
 
-def write_ply(path, vertices, triangles):
-    """Binary little-endian PLY with float32 vertices and int32 triangles (the layout trimesh exports for a bare mesh)."""
+def transform_normals(normals, matrix):
+    """normals (V,3), matrix (4,4) -> (V,3) float64: the normals of a surface moved by transform_vertices(., matrix).  Normals go with the
+    inverse transpose of the linear part -- `n @ inv(M[:3, :3])` on row vectors -- and are renormalised: scale_mat need not be a uniform
+    scale.  Zero rows (no normal) stay zero."""
+    m = np.asarray(matrix, dtype=np.float64)
+    n = np.asarray(normals, dtype=np.float64).reshape(-1, 3) @ np.linalg.inv(m[:3, :3])
+    length = np.linalg.norm(n, axis=1, keepdims=True)
+    return np.divide(n, length, out=np.zeros_like(n), where=length > 0)
+
+
+def write_ply(path, vertices, triangles, normals=None, colors=None):
+    """Binary little-endian PLY with float32 vertices and int32 triangles (the layout trimesh exports for a bare mesh).
+    normals (V,3) / colors (V,3): optional per-vertex properties, written as float nx ny nz / uchar red green blue after x y z (the names
+    MeshLab, Open3D and trimesh read)."""
     v = np.ascontiguousarray(vertices, dtype="<f4").reshape(-1, 3)
     t = np.ascontiguousarray(triangles, dtype="<i4").reshape(-1, 3)
     if t.size and (t.min() < 0 or t.max() >= len(v)):
         raise ValueError("write_ply: triangle index out of range")
+    fields, names = [("xyz", "<f4", (3,))], "property float x\nproperty float y\nproperty float z\n"
+    if normals is not None:
+        normals = np.asarray(normals).reshape(-1, 3)
+        fields.append(("n", "<f4", (3,)))
+        names += "property float nx\nproperty float ny\nproperty float nz\n"
+    if colors is not None:
+        colors = np.asarray(colors).reshape(-1, 3)
+        fields.append(("c", "u1", (3,)))
+        names += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    for what, a in (("normals", normals), ("colors", colors)):
+        if a is not None and len(a) != len(v):
+            raise ValueError(f"write_ply: {len(a)} {what} for {len(v)} vertices")
     header = ("ply\nformat binary_little_endian 1.0\ncomment gens_amd\n"
-              f"element vertex {len(v)}\nproperty float x\nproperty float y\nproperty float z\n"
+              f"element vertex {len(v)}\n{names}"
               f"element face {len(t)}\nproperty list uchar int vertex_indices\nend_header\n")
+    if len(fields) > 1:
+        rows = np.empty(len(v), dtype=fields)
+        rows["xyz"] = v
+        if normals is not None:
+            rows["n"] = normals
+        if colors is not None:
+            rows["c"] = colors
+        v = rows
     faces = np.empty(len(t), dtype=[("n", "u1"), ("idx", "<i4", (3,))])
     faces["n"] = 3
     faces["idx"] = t
@@ -46,10 +78,12 @@ _PLY_TYPES = {b"char": "i1", b"int8": "i1", b"uchar": "u1", b"uint8": "u1", b"sh
               b"float64": "<f8"}
 
 
-def read_ply(path):
+def read_ply(path, attributes=False):
     """Inverse of write_ply (binary little-endian, x/y/z vertices, uchar-counted int triangles) -> (vertices, triangles).  Also reads what
     the DTU scoring reads (evaluation/dtu_eval.py:84, 122): a file whose vertices carry further scalar properties (normals, colours), and a
-    point cloud without a face element, which gives triangles of shape (0, 3).  The vertices keep the file's x/y/z type."""
+    point cloud without a face element, which gives triangles of shape (0, 3).  The vertices keep the file's x/y/z type.
+    attributes=True: -> (vertices, triangles, attrs), attrs holding "normals" (V,3) from nx ny nz and "colors" (V,3) from red green blue, in
+    the file's types, where the file has them."""
     with open(path, "rb") as f:
         if f.readline().strip() != b"ply":
             raise ValueError(f"{path}: not a PLY file")
@@ -88,7 +122,13 @@ def read_ply(path):
         faces = np.frombuffer(f.read(13 * nf), dtype=[("n", "u1"), ("idx", "<i4", (3,))])
         if nf and not (faces["n"] == 3).all():
             raise ValueError(f"{path}: non-triangular face")
-    return v.copy(), faces["idx"].copy()
+    if not attributes:
+        return v.copy(), faces["idx"].copy()
+    have, attrs = [p for p, _ in props], {}
+    for key, cols in (("normals", ("nx", "ny", "nz")), ("colors", ("red", "green", "blue"))):
+        if all(c in have for c in cols):
+            attrs[key] = np.stack([rows[c] for c in cols], axis=-1)
+    return v.copy(), faces["idx"].copy(), attrs
 
 
 @torch.no_grad()
@@ -111,17 +151,18 @@ def clean_mesh_by_mask(vertices, triangles, masks, intrs, c2ws, min_nb_visible=1
     return np.asarray(triangles)[valid[tri].all(dim=-1).numpy()]
 
 
-def drop_small_components(vertices, triangles, min_faces=500):
+def drop_small_components(vertices, triangles, min_faces=500, return_index=False):
     """utils/clean_mesh.py:101-106 without trimesh, on the host: keep the connected components (faces sharing an edge) of at least
     `min_faces` faces and drop the vertices nothing references any more -> (vertices, triangles) re-indexed.  Faces are joined across
     every shared edge, also one that more than two faces share; trimesh's face_adjacency (and clean_mesh_outside_frustum) joins only
-    across edges of exactly two faces.  On manifold meshes the two agree."""
+    across edges of exactly two faces.  On manifold meshes the two agree.
+    return_index: also the (V',) int64 indices of the kept vertices in `vertices` (per-vertex attributes follow with attrs[index])."""
     from scipy.sparse import coo_matrix
     from scipy.sparse.csgraph import connected_components
     tri = np.asarray(triangles, dtype=np.int64).reshape(-1, 3)
     v = np.asarray(vertices)
     if len(tri) == 0:
-        return v[:0], tri
+        return (v[:0], tri, np.zeros(0, dtype=np.int64)) if return_index else (v[:0], tri)
     # faces adjacent through a shared (undirected) edge: sort the three edges of every face, group equal edges
     edges = np.sort(np.stack([tri[:, [0, 1]], tri[:, [1, 2]], tri[:, [2, 0]]], 1).reshape(-1, 2), axis=1)
     face_of = np.repeat(np.arange(len(tri)), 3)
@@ -135,7 +176,8 @@ def drop_small_components(vertices, triangles, min_faces=500):
     used = np.zeros(len(v), dtype=bool)
     used[tri.reshape(-1)] = True
     remap = np.cumsum(used) - 1
-    return v[used], remap[tri].astype(np.asarray(triangles).dtype if len(tri) else np.int64)
+    mesh = v[used], remap[tri].astype(np.asarray(triangles).dtype if len(tri) else np.int64)
+    return mesh + (np.flatnonzero(used).astype(np.int64),) if return_index else mesh
 
 
 def as_numpy(x):
@@ -153,7 +195,7 @@ def device_of(*xs, device=None):
 
 
 @torch.no_grad()
-def clean_mesh_outside_frustum(vertices, triangles, masks, intrs, c2ws, upscale=4, min_faces=500):
+def clean_mesh_outside_frustum(vertices, triangles, masks, intrs, c2ws, upscale=4, min_faces=500, return_index=False):
     """utils/clean_mesh.py:38-106 on the device (K23): keep the faces that some masked pixel of some view (upsampled by `upscale`) sees
     first, then the connected components of at least `min_faces` faces, then the referenced vertices (in their order, as trimesh's
     remove_unreferenced_vertices).  vertices (V,3), triangles (F,3) (arrays or tensors), masks (nv,H,W) raw (a pixel casts iff its
@@ -165,7 +207,8 @@ def clean_mesh_outside_frustum(vertices, triangles, masks, intrs, c2ws, upscale=
     component at all (trimesh takes the graph's nodes from its edges).  One deliberate deviation: where no component survives, the
     reference raises inside np.concatenate([]); this returns an empty mesh.  trimesh also merges coincident vertices when it loads a
     mesh; K12 emits one vertex per lattice edge, so vertices coincide only where a lattice value equals the threshold exactly, and no
-    merge is done here."""
+    merge is done here.
+    return_index: also the (V',) int64 indices of the returned vertices in `vertices`."""
     from . import ops
     v_np, t_np = as_numpy(vertices), as_numpy(triangles)
     dev = device_of(vertices, triangles, masks)
@@ -175,32 +218,33 @@ def clean_mesh_outside_frustum(vertices, triangles, masks, intrs, c2ws, upscale=
         grid = ops.build_mesh_grid(v, t)
         flags, any_miss = ops.visible_faces(grid, masks, intrs, c2ws, upscale)       # the union over the views: one view's counts
         t = t[ops.kept_after_quirk(flags, any_miss, 1)[0]]
-    return ops.large_components(v_np, t_np.dtype, t, min_faces)
+    return ops.large_components(v_np, t_np.dtype, t, min_faces, return_index=return_index)
 
 
 @torch.no_grad()
-def _drop_small_components_device(vertices, triangles, min_faces=500):
+def _drop_small_components_device(vertices, triangles, min_faces=500, return_index=False):
     """clean_mesh.py:101-106 on the device (K23), trimesh's rule: faces are joined across edges of exactly two faces, and a face without
     such a neighbour is in no component -> (vertices, triangles) numpy, unreferenced vertices removed in their order.  Equal to
-    `drop_small_components` on manifold meshes (for min_faces >= 2)."""
+    `drop_small_components` on manifold meshes (for min_faces >= 2).  return_index: also the kept vertices' (V',) int64 indices."""
     from . import ops
     v_np, t_np = as_numpy(vertices), as_numpy(triangles)
     dev = device_of(vertices, triangles)
-    return ops.large_components(v_np, t_np.dtype, torch.as_tensor(t_np.astype(np.int64)).reshape(-1, 3).to(dev), min_faces)
+    return ops.large_components(v_np, t_np.dtype, torch.as_tensor(t_np.astype(np.int64)).reshape(-1, 3).to(dev), min_faces, return_index=return_index)
 
 
 @torch.no_grad()
-def clean_mesh(vertices, triangles, masks, intrs, c2ws, dilation_radius=11, min_nb_visible=1, upscale=2, min_faces=500):
+def clean_mesh(vertices, triangles, masks, intrs, c2ws, dilation_radius=11, min_nb_visible=1, upscale=2, min_faces=500, return_index=False):
     """utils/clean_mesh.py:109-130: masks (nv,H,W[,3]) are averaged over a trailing channel axis; the faces outside the dilated (> 0.5)
     masks go (clean_mesh_by_mask, on the host), then clean_mesh_outside_frustum runs with the un-dilated averaged masks -> (vertices,
     triangles) numpy, unreferenced vertices removed (see clean_mesh_outside_frustum for the quirks kept and the one deviation).
-    min_faces: the component size of clean_mesh.py:102 (500 there, not an argument of the reference's clean_mesh)."""
+    min_faces: the component size of clean_mesh.py:102 (500 there, not an argument of the reference's clean_mesh).
+    return_index: also the (V',) int64 indices of the returned vertices in `vertices` (the mask half drops faces only)."""
     masks = masks.detach().cpu()
     if masks.dim() > 3:
         masks = masks.mean(dim=-1)
     v_np = as_numpy(vertices)
     kept = clean_mesh_by_mask(v_np, as_numpy(triangles), dilate_masks(masks, dilation_radius), intrs, c2ws, min_nb_visible)
-    return clean_mesh_outside_frustum(v_np, kept, masks, intrs, c2ws, upscale=upscale, min_faces=min_faces)
+    return clean_mesh_outside_frustum(v_np, kept, masks, intrs, c2ws, upscale=upscale, min_faces=min_faces, return_index=return_index)
 
 
 def dilate_masks(masks, radius=11):
@@ -232,22 +276,32 @@ def save_validation_outputs(base_exp_dir, outputs, inputs, tag, image_tag=None, 
     runner.py:349-375 (tag = "step{s}", image_tag = the view index) do.  Returns the written paths.
     clean=True: the mask half of the cleaning only; clean=True, clean_frustum=True: the whole of utils/clean_mesh.py's clean_mesh
     (`clean_mesh`, what runner.py --clean_mesh scores).  clean_frustum=True without clean=True is an error (the frustum step runs on
-    the mask half's result)."""
+    the mask half's result).
+    outputs["vertex_normals"] / ["vertex_colors"] (validate's mesh_attributes), where present, follow the mesh: through the cleaning's
+    vertex index, the normals through transform_normals; colours of vertices no source view sees (outputs["vertex_seen"] False: the network's
+    output is arbitrary there) are written mid-grey (128, 128, 128)."""
     if clean_frustum and not clean:
         raise ValueError("save_validation_outputs: clean_frustum=True needs clean=True")
     scene = inputs["scene"]
     image_tag = inputs["file_name"] if image_tag is None else image_tag
     vertices, triangles = outputs["vertices"], outputs["triangles"]
+    normals, colors = outputs.get("vertex_normals"), outputs.get("vertex_colors")
+    if colors is not None and outputs.get("vertex_seen") is not None:
+        colors = np.where(np.asarray(outputs["vertex_seen"], dtype=bool)[:, None], colors, np.uint8(128))
     if clean and clean_frustum:
-        vertices, triangles = clean_mesh(vertices, triangles, inputs["masks"], inputs["intrs"], inputs["c2ws"])
+        vertices, triangles, index = clean_mesh(vertices, triangles, inputs["masks"], inputs["intrs"], inputs["c2ws"], return_index=True)
+        normals, colors = (None if a is None else np.asarray(a)[index] for a in (normals, colors))
     elif clean:
         triangles = clean_mesh_by_mask(vertices, triangles, dilate_masks(inputs["masks"]), inputs["intrs"], inputs["c2ws"])
-    vertices = transform_vertices(vertices, inputs["scale_mat"].detach().cpu().numpy())
+    scale_mat = inputs["scale_mat"].detach().cpu().numpy()
+    vertices = transform_vertices(vertices, scale_mat)
+    if normals is not None:
+        normals = transform_normals(normals, scale_mat)
     paths = {}
     for sub in ("meshes", "val_img", "val_normal", "val_sdf_depth", "val_render_depth"):
         os.makedirs(os.path.join(base_exp_dir, sub), exist_ok=True)
     paths["mesh"] = os.path.join(base_exp_dir, "meshes", f"{scene}_{tag}.ply")
-    write_ply(paths["mesh"], vertices, triangles)
+    write_ply(paths["mesh"], vertices, triangles, normals=normals, colors=colors)
     paths["img"] = os.path.join(base_exp_dir, "val_img", f"{image_tag}_{tag}.png")
     Image.fromarray(outputs["img_fine"].astype(np.uint8)).save(paths["img"])
     paths["normal"] = os.path.join(base_exp_dir, "val_normal", f"{image_tag}_{tag}.png")

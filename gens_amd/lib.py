@@ -208,6 +208,8 @@ SIGNATURES = {
     "gens_brick_emit_flags": [_p, _i, _i, _p, _p],
     "gens_brick_mc_classify": [_p, _p, _p, _p, _i, _i, _p, _l, _f, _p, _p, _p, _p, _p, _p],
     "gens_brick_mc_emit": [_p, _p, _p, _p, _i, _i, _p, _l, _f, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
+    "gens_vertex_points": [_p, _l, _i, _d, _d, _d, _d, _d, _d, _p, _p],
+    "gens_vertex_pack": [_p, _p, _p, _i, _l, _p, _p, _p, _p],
 }
 
 _lib = None

@@ -97,6 +97,9 @@ class GenS(nn.Module):
         mesh = confs.get("sparse_mesh", None)                   # optional: marching cubes on that lattice's bricks, no dense lattice (K29)
         if mesh is not None:
             self.implicit_surface.sparse_mesh = bool(mesh)
+        attrs = confs.get("mesh_attributes", None)              # optional: per-vertex "normals" / "colors" on extracted meshes (K30); a name or a list
+        if attrs is not None:
+            self.implicit_surface.mesh_attributes = (attrs,) if isinstance(attrs, str) else tuple(attrs)
         lipschitz = confs.get("lattice_lipschitz", None)        # optional: the bound that lattice assumes (ImplicitSurface.lattice_lipschitz)
         if lipschitz is not None:
             self.implicit_surface.lattice_lipschitz = float(lipschitz)

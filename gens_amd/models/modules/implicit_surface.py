@@ -575,6 +575,9 @@ class ImplicitSurface(nn.Module):
     SPARSE_BRICK = 4               # what `sparse=True` means: the brick edge that measured best at 512^3 and 1024^3
     sparse_mesh = None             # True: extract_geometry runs marching cubes on the sparse lattice's bricks (ops.brick_marching_cubes, K29) and
                                    # builds no dense lattice; needs a sparse brick of 2 to 8 cells.  None / False: off
+    mesh_attributes = None         # ("normals", "colors") or one of them: extract_geometry / validate also return per-vertex attributes
+                                   # (vertex_attributes, K30).  None / (): off
+    VERTEX_ATTRIBUTES = ("normals", "colors")
 
     def _lattice_route(self, sparse, sparse_mesh, shard):
         """The options of sdf_grid (sparse_mesh=False) and extract_geometry -> (route, brick edge): "dense" (the dense lattice, brick None),
@@ -607,14 +610,17 @@ class ImplicitSurface(nn.Module):
             return unsharded("_warned_sparse_shard", "the sparse lattice is not sharded: with a shard the dense lattice is evaluated")
         return "lattice", brick
 
-    def _lattice_passes(self, vols, shard, run):
-        """run(evaluate) with the lattice's evaluator (the fused plan and this scene's precision, else the PyTorch layers) -> its result.  A
+    def _lattice_passes(self, vols, shard, run, want_grad=False):
+        """run(evaluate) with the SDF evaluator of the mesh passes (the fused plan and this scene's precision, else the PyTorch layers) -> its
+        result.  evaluate(pts) -> sdf, or (sdf, gradient) with want_grad (the fused plan only: vertex_attributes checks for it).  A
         split-half launch that met a value outside the half range repeats the WHOLE run in float32, like the image."""
         split_half = None
         for _ in range(2):
             def evaluate(pts):
                 plan = self._fused_plan(vols)
-                prec = "f32" if split_half is False else self._precision(plan) if plan is not None else "f32"
+                prec = "f32" if split_half is False else self._precision(plan, want_grad) if plan is not None else "f32"
+                if want_grad:
+                    return ops.sdf_mlp(plan, vols, pts, want_grad=True, precision=prec)
                 return ops.sdf_mlp(plan, vols, pts, precision=prec) if plan is not None else self.sdf_network.sdf(pts, vols)
 
             out = run(evaluate)
@@ -689,13 +695,98 @@ class ImplicitSurface(nn.Module):
                                "are beyond the dense lattice (2^31): raise lattice_lipschitz")
         return None
 
-    def extract_geometry(self, volumes, bound_min, bound_max, resolution, threshold, shard=None, sparse=None, sparse_mesh=None):
+    def _attribute_request(self, attributes, volumes, views):
+        """The attributes a mesh call asks for (None: the attribute `mesh_attributes`; a name or a sequence of names) -> a tuple in the order
+        of VERTEX_ATTRIBUTES, () for none.  Raises ValueError, before anything is launched, for what vertex_attributes cannot serve: an
+        unknown name, colours without views, volumes or networks outside the fused kernels."""
+        attributes = self.mesh_attributes if attributes is None else attributes
+        if attributes is None:
+            return ()
+        names = (attributes,) if isinstance(attributes, str) else tuple(attributes)
+        unknown = [a for a in names if a not in self.VERTEX_ATTRIBUTES]
+        if unknown:
+            raise ValueError(f"mesh attributes {unknown!r}: the known ones are {self.VERTEX_ATTRIBUTES!r}")
+        names = tuple(a for a in self.VERTEX_ATTRIBUTES if a in names)
+        if not names:
+            return ()
+        if "colors" in names and views is None:
+            raise ValueError('mesh attributes: "colors" needs the scene\'s views (views=scene.views): the colour is a function of the point and the views')
+        if "normals" in names:
+            packed = isinstance(volumes, ops.VolumeSet)
+            n_levels = volumes.n if packed else len(volumes)
+            net = self.sdf_network
+            if not 1 <= n_levels <= 5 or (packed and volumes.layout != 1):
+                raise ValueError(f"mesh attributes: the fused SDF kernels take 1 to 5 packed volume levels, not {n_levels}"
+                                 f"{'' if not packed or volumes.layout == 1 else ' planar ones'}; there is no other route for the normals")
+            if not self.fused_sdf or not ops.SdfMlpPlan.supported(net) or net.init_feat_channels != 4 * n_levels:
+                raise ValueError("mesh attributes: the normals need the fused SDF kernels (fused_sdf, the shipped SDF architecture, "
+                                 f"init_feat_channels = 4 x {n_levels} levels)")
+        if "colors" in names:
+            if not isinstance(views, ops.SceneViews):
+                raise ValueError("mesh attributes: views is the scene's ops.SceneViews (Scene.views)")
+            with torch.no_grad():
+                if self._fused_blend_plan(views) is None:
+                    raise ValueError("mesh attributes: the colours need the fused blending kernel (fused_blend, the shipped colour network, at most "
+                                     "5 feature levels that match its width)")
+        return names
+
+    @torch.no_grad()
+    def vertex_attributes(self, points, volumes, views=None, attributes=("normals", "colors"), chunk=1 << 21):
+        """Per-vertex attributes of a mesh in the model's frame.  points (V,3), numpy or tensor, float32 or float64 (evaluated as float32),
+        from anywhere: an extracted mesh, a cleaned one, a file.  -> dict of numpy arrays, limited to what `attributes` names:
+            "normals" (V,3) float32: grad sdf / |grad sdf| (zero rows where the gradient is zero or not finite) -- the shading normal;
+            "colors"  (V,3) uint8:   the blending network's output at the point in validate's img_fine convention, trunc(clip(256 c, 0, 255));
+            "seen"    (V,) bool (with "colors"): some source view has the point in its frustum; elsewhere the colour is arbitrary.
+        Per chunk: ops.sdf_mlp(want_grad=True), ops.blend_views, ops.vertex_pack (K30).  The evaluator is the lattice's (_lattice_passes): this
+        scene's precision, and a split-half overflow repeats the whole pass in float32.  No mask volume is consulted (the lattice is not
+        masked either).  ValueError before any launch where the fused kernels do not apply (_attribute_request): there is no slow route."""
+        names = self._attribute_request(attributes, volumes, views)
+        vols = volumes if isinstance(volumes, ops.VolumeSet) else ops.VolumeSet.packed(volumes)
+        dev = vols.tensors[0].device
+        pts = torch.as_tensor(points).detach().reshape(-1, 3).to(device=dev, dtype=torch.float32).contiguous()
+        n, chunk = pts.shape[0], max(1, int(chunk))
+        want_n, want_c = "normals" in names, "colors" in names
+        if want_n and self._fused_plan(vols) is None:      # (what _attribute_request could not see before the volumes were packed)
+            raise ValueError("mesh attributes: the normals need the fused SDF kernels; these volumes do not take them")
+        bplan = self._fused_blend_plan(views) if want_c else None
+        normals = torch.empty(n, 3, device=dev, dtype=torch.float32) if want_n else None
+        colors = torch.empty(n, 3, device=dev, dtype=torch.uint8) if want_c else None
+        seen = torch.empty(n, device=dev, dtype=torch.uint8) if want_c else None
+
+        def run(evaluate):
+            for s in range(0, n, chunk):
+                e = min(s + chunk, n)
+                grad = evaluate(pts[s:e])[1] if want_n else None
+                rgb, vis = ops.blend_views(bplan, views, pts[s:e]) if want_c else (None, None)
+                ops.vertex_pack(grad, rgb, vis, normals=normals[s:e] if want_n else None, colors=colors[s:e] if want_c else None,
+                                seen=seen[s:e] if want_c else None)
+
+        if n and names:
+            if want_n:
+                self._lattice_passes(vols, None, run, want_grad=True)
+            else:
+                run(None)
+        out = {}
+        if want_n:
+            out["normals"] = normals.cpu().numpy()
+        if want_c:
+            out["colors"] = colors.cpu().numpy()
+            out["seen"] = seen.cpu().numpy().astype(bool)
+        return out
+
+    def extract_geometry(self, volumes, bound_min, bound_max, resolution, threshold, shard=None, sparse=None, sparse_mesh=None, attributes=None,
+                         views=None):
         """-> vertices (V,3) float64, triangles (T,3) int32 as numpy arrays (implicit_surface.py:407-427).  The SDF lattice and
         the marching cubes both run on the device (the reference: 512 D2H copies + PyMCubes on the host); only the mesh is copied.
         sparse: sdf_grid's option of that name, with this call's threshold.  sparse_mesh (default: the attribute of that name, None = off):
         together with a sparse brick of 2 to 8 cells, marching cubes runs on the bricks (ops.brick_marching_cubes) and no dense lattice is
         built -- the same mesh, resolutions beyond 1290 included.  A leak count above zero warns and takes the dense lattice (RuntimeError
-        where resolution^3 >= 2^31 leaves none); with a shard the option is ignored with one warning."""
+        where resolution^3 >= 2^31 leaves none); with a shard the option is ignored with one warning.
+        attributes (default: the attribute `mesh_attributes`, None / () = off): "normals", "colors" or both -> a third result, the dict of
+        vertex_attributes at the float32 rounding of the returned vertices (formed on the device, gens_vertex_points, before the mesh is
+        copied); views: the scene's ops.SceneViews, needed for the colours.  The same pass on every route, the leak fallback included; with a
+        shard, on every rank that holds the gathered mesh."""
+        attributes = self._attribute_request(attributes, volumes, views)
         route, brick = self._lattice_route(sparse, sparse_mesh, shard)
         mesh = None
         if route == "mesh":
@@ -708,23 +799,28 @@ class ImplicitSurface(nn.Module):
         else:
             u = self.sdf_grid(volumes, bound_min, bound_max, resolution, shard=shard, sparse=sparse, threshold=threshold)
             if u is None:
-                return None, None
+                return (None, None, None) if attributes else (None, None)
             mesh = ops.marching_cubes(u, threshold)
         vertices, triangles = mesh
-        vertices, triangles = vertices.cpu().numpy(), triangles.cpu().numpy()
         b_max, b_min = bound_max.detach().cpu().numpy(), bound_min.detach().cpu().numpy()
+        attrs = None
+        if attributes:                                 # on the device-resident vertices; span: the host expression's (float32) difference, widened
+            points = ops.vertex_points(vertices, resolution, (b_max - b_min).astype(np.float64).tolist(), b_min.astype(np.float64).tolist())
+            attrs = self.vertex_attributes(points, volumes, views, attributes)
+        vertices, triangles = vertices.cpu().numpy(), triangles.cpu().numpy()
         vertices = vertices / (resolution - 1.0) * (b_max - b_min)[None, :] + b_min[None, :]
-        return vertices, triangles
+        return (vertices, triangles, attrs) if attributes else (vertices, triangles)
 
     @torch.no_grad()
     def validate(self, rays_o, rays_d, near, far, volumes, mask_volumes, imgs, features, match_features, intrs, c2ws, bound_min, bound_max,
                  hw, cos_anneal_ratio=1.0, step=None, extract_geometry=True, mesh_resolution=512, threshold=0.0, scene=None, shard=None, sparse=None,
-                 sparse_mesh=None):
+                 sparse_mesh=None, mesh_attributes=None):
         """shard (gens_amd.distributed.Shard, optional): render only this rank's contiguous ray range and evaluate only its lattice
         chunks; the (P, 8) image buffer / the lattice slabs are gathered over RCCL, so every rank returns the whole image.  The jitter
         of EVERY ray is drawn on every rank from the identically seeded CPU generator (the reference's draw order) and sliced with
         the rays: the image does not depend on the partition.  sparse, sparse_mesh: extract_geometry's options (the two-level lattice, marching cubes
-        on its bricks)."""
+        on its bricks).  mesh_attributes: extract_geometry's `attributes` with this scene's views -> outputs["vertex_normals"],
+        ["vertex_colors"], ["vertex_seen"] beside the mesh."""
         outputs = {}
         if scene is None:
             scene = Scene(volumes, mask_volumes, imgs, features, match_features, intrs, c2ws)
@@ -743,9 +839,11 @@ class ImplicitSurface(nn.Module):
         if extract_geometry:
             import time
             t_geo = time.perf_counter()
-            outputs["vertices"], outputs["triangles"] = self.extract_geometry(scene.volumes_nograd(), bound_min, bound_max, mesh_resolution,
-                                                                              threshold, shard=shard, sparse=sparse,
-                                                                              sparse_mesh=sparse_mesh)
+            mesh = self.extract_geometry(scene.volumes_nograd(), bound_min, bound_max, mesh_resolution, threshold, shard=shard, sparse=sparse,
+                                         sparse_mesh=sparse_mesh, attributes=mesh_attributes, views=scene.views)
+            outputs["vertices"], outputs["triangles"] = mesh[0], mesh[1]
+            for name, values in ((mesh[2] or {}) if len(mesh) == 3 else {}).items():
+                outputs["vertex_" + name] = values
             self.last_geometry_s = time.perf_counter() - t_geo     # (ends with the mesh's read-back: wall time is the item's share; bench.py's default_path)
         # one (P, 8) device buffer [rgb | normal | sdf_depth | render_depth] filled chunk by chunk: ONE D2H copy per image
         # into a pinned host buffer (the reference copies 4 tensors per 256-ray chunk, implicit_surface.py:446-453)

@@ -24,6 +24,7 @@ is what it was when ops was one module:
     ops.lattice   K28: the two-level SDF lattice of extract_geometry, evaluated near the iso-surface only (sparse_lattice), and what K29
                   shares with it: dimensions, point and classify launches under either set of limits, the front end of both.
     ops.brick_mcubes  K29: marching cubes on that lattice's bricks, without the dense lattice (brick_marching_cubes).
+    ops.vertex_attrs  K30: per-vertex attributes of an extracted mesh: lattice vertices to points, gradient / colour to normals / 8-bit colours.
 """
 from .base import *  # noqa: F401,F403
 from .volume import *  # noqa: F401,F403
@@ -40,3 +41,4 @@ from .finalize import *  # noqa: F401,F403
 from .filter import *  # noqa: F401,F403
 from .lattice import *  # noqa: F401,F403
 from .brick_mcubes import *  # noqa: F401,F403
+from .vertex_attrs import *  # noqa: F401,F403

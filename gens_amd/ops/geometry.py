@@ -260,10 +260,11 @@ def kept_after_quirk(counts, any_miss, num_com_vis=2):
     return keep, n_values
 
 
-def large_components(v_np, t_dtype, t, min_faces):
+def large_components(v_np, t_dtype, t, min_faces, return_index=False):
     """The tail of both cleaning scripts (clean_mesh.py:101-106, clean_meshes.py:268-281) on device triangles t (F,3) int64 over the host
     vertices v_np: the components of at least `min_faces` faces by trimesh's rule (a face without a neighbour across an edge of exactly
-    two faces is in no component), then the referenced vertices in their order -> (vertices, triangles of t_dtype) numpy."""
+    two faces is in no component), then the referenced vertices in their order -> (vertices, triangles of t_dtype) numpy.
+    return_index: also the (V',) int64 indices of the kept vertices in v_np, for per-vertex attributes to follow the compaction."""
     dev, n_v = t.device, len(v_np)
     if len(t):
         pairs = face_adjacency(t, n_v)
@@ -274,7 +275,12 @@ def large_components(v_np, t_dtype, t, min_faces):
     used = torch.zeros(n_v, device=dev, dtype=torch.bool)
     used[t.reshape(-1)] = True
     remap = torch.cumsum(used, 0) - 1
-    return v_np.reshape(-1, 3)[used.cpu().numpy()], remap[t].cpu().numpy().astype(t_dtype)
+    used_np = used.cpu().numpy()
+    mesh = v_np.reshape(-1, 3)[used_np], remap[t].cpu().numpy().astype(t_dtype)
+    if return_index:
+        import numpy as np
+        return mesh + (np.flatnonzero(used_np).astype(np.int64),)
+    return mesh
 
 
 __all__ = [n_ for n_ in dir() if not n_.startswith("__")]      # private helpers travel too: the package namespace is the old module's

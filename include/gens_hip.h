@@ -61,7 +61,8 @@ const char* gens_last_error(void);
  *       gens_dilate_u8, gens_vertex_mask_votes, gens_view_rays_hit_counts, and K26's gens_filter_masks, gens_filter_band, gens_filter_levels,
  *       and K27's gens_largest_component, gens_components_scratch_bytes, gens_unpack_mask_bits, and K28's gens_sparse_coarse_points,
  *       gens_sparse_classify, gens_sparse_brick_points, gens_sparse_fill, gens_sparse_scatter, gens_sparse_leaks, and K29's
- *       gens_brick_coarse_points, gens_brick_points, gens_brick_active, gens_brick_emit_flags, gens_brick_mc_classify, gens_brick_mc_emit. */
+ *       gens_brick_coarse_points, gens_brick_points, gens_brick_active, gens_brick_emit_flags, gens_brick_mc_classify, gens_brick_mc_emit,
+ *       and K30's gens_vertex_points, gens_vertex_pack. */
 int gens_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -905,6 +906,27 @@ int gens_brick_mc_emit(const float* uc, const float* store, const int32_t* pslot
                        int64_t n_list, float iso, const int8_t* tri_table, int table_stride, const uint8_t* tri_count, const uint8_t* vmask,
                        const uint8_t* cases, const uint16_t* rank, const int64_t* voff, const int64_t* toff, double* vertices,
                        int32_t* triangles, int64_t* vkey, int64_t* tkey, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * K30  Per-vertex attributes of an extracted mesh (ImplicitSurface.vertex_attributes): the two streaming launches around the network
+ *      kernels (gens_sdf_grad*, gens_blend_views*), csrc/k30_vertex_attrs.hip.  Arguments are checked before any launch: a negative n,
+ *      resolution < 2, a null pointer that n > 0 would dereference, n_src outside 1 .. 255: GENS_EINVAL; n >= 2^31: GENS_ELIMIT.  n == 0
+ *      succeeds without a launch.  The ABI version stays 12: no existing entry changes.
+ *   gens_vertex_points: vertices (n, 3) float64 in lattice-index coordinates (gens_mc_emit / gens_brick_mc_emit) -> points (n, 3) float32 =
+ *     the float32 rounding of v / (resolution - 1.0) * span + lo, evaluated per component in float64 in that order, un-fused: the
+ *     vertices extract_geometry returns (implicit_surface.py:424-425), rounded once.  span / lo: the box's extent and lower corner as the
+ *     caller's float64 arithmetic sees them (extract_geometry: the float32 difference b_max - b_min widened).
+ *   gens_vertex_pack: grad (n, 3) float32 = d sdf / dx, color (n, 3) float32, vis (n, n_src) uint8 in-frustum flags ->
+ *     normals (n, 3) float32 = g / sqrt((gx^2 + gy^2) + gz^2) in float64, rounded once; (0, 0, 0) where a component is not finite or the
+ *       norm is 0 (a gradient whose float32 squares would underflow still normalises);
+ *     colors (n, 3) uint8 = trunc(min(max(c * 256, 0), 255)) (implicit_surface.py:455), 0 for a component that is not finite;
+ *     seen (n) uint8 = 1 if any of the vertex' n_src flags is set.
+ *     grad == NULL: normals is not written; color == NULL: colors and seen are not written (vis is not read).  Both NULL: GENS_EINVAL.
+ * ---------------------------------------------------------------------------------------------------------- */
+int gens_vertex_points(const double* vertices, int64_t n, int resolution, double span_x, double span_y, double span_z, double lo_x,
+                       double lo_y, double lo_z, float* points, void* stream);
+int gens_vertex_pack(const float* grad, const float* color, const uint8_t* vis, int n_src, int64_t n, float* normals, uint8_t* colors,
+                     uint8_t* seen, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K14  C (m x n) = A^T B for tall row-major operands A (k x m), B (k x n), k >> m, n: the weight-gradient product of the training
