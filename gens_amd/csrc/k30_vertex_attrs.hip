@@ -12,6 +12,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "pack_rules.h"
 
 #pragma clang fp contract(off)
 
@@ -34,28 +35,15 @@ __global__ __launch_bounds__(256) void vertex_pack_k(const float* __restrict__ g
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     if (grad) {
-        const double gx = grad[3 * i], gy = grad[3 * i + 1], gz = grad[3 * i + 2];
-        const double norm = sqrt((gx * gx + gy * gy) + gz * gz);        // (float32 squares are exact in double and cannot overflow it)
-        float nx = 0.f, ny = 0.f, nz = 0.f;
-        if (isfinite(gx) && isfinite(gy) && isfinite(gz) && norm > 0.0) {
-            nx = (float)(gx / norm);
-            ny = (float)(gy / norm);
-            nz = (float)(gz / norm);
-        }
+        float nx, ny, nz;
+        gens_unit_normal(grad[3 * i], grad[3 * i + 1], grad[3 * i + 2], nx, ny, nz);
         normals[3 * i] = nx;
         normals[3 * i + 1] = ny;
         normals[3 * i + 2] = nz;
     }
     if (color) {
-        for (int a = 0; a < 3; ++a) {
-            const float c = color[3 * i + a];
-            uint8_t q = 0;
-            if (isfinite(c)) q = (uint8_t)(int)fminf(fmaxf(c * 256.f, 0.f), 255.f);       // (c * 256 is exact or overflows to an infinity the clamp takes)
-            colors[3 * i + a] = q;
-        }
-        unsigned any = 0;
-        for (int s = 0; s < n_src; ++s) any |= vis[i * n_src + s];
-        seen[i] = any ? 1 : 0;
+        for (int a = 0; a < 3; ++a) colors[3 * i + a] = gens_color8(color[3 * i + a]);
+        seen[i] = gens_any_flag(vis + i * n_src, n_src);
     }
 }
 

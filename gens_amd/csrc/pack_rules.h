@@ -1,0 +1,33 @@
+// The per-point pack rules K30 (gens_vertex_pack) and K31 (gens_surface_pack) share: one definition, the same bits in both.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#pragma clang fp contract(off)
+
+// g / sqrt((gx^2 + gy^2) + gz^2) in float64, rounded once per component; (0, 0, 0) where a component is not finite or the norm is 0.
+// (float32 squares are exact in double and cannot overflow it, so no float32 square root or rescaling enters the result)
+__device__ __forceinline__ void gens_unit_normal(float fx, float fy, float fz, float& nx, float& ny, float& nz) {
+    const double gx = fx, gy = fy, gz = fz;
+    const double norm = sqrt((gx * gx + gy * gy) + gz * gz);
+    nx = ny = nz = 0.f;
+    if (isfinite(gx) && isfinite(gy) && isfinite(gz) && norm > 0.0) {
+        nx = (float)(gx / norm);
+        ny = (float)(gy / norm);
+        nz = (float)(gz / norm);
+    }
+}
+
+// validate's img_fine convention (implicit_surface.py:455): trunc(min(max(c * 256, 0), 255)); 0 for a component that is not finite.
+__device__ __forceinline__ uint8_t gens_color8(float c) {
+    uint8_t q = 0;
+    if (isfinite(c)) q = (uint8_t)(int)fminf(fmaxf(c * 256.f, 0.f), 255.f);       // (c * 256 is exact or overflows to an infinity the clamp takes)
+    return q;
+}
+
+// 1 if any of the n_src in-frustum flags of a row is set.
+__device__ __forceinline__ uint8_t gens_any_flag(const uint8_t* __restrict__ row, int n_src) {
+    unsigned any = 0;
+    for (int s = 0; s < n_src; ++s) any |= row[s];
+    return any ? 1 : 0;
+}

@@ -279,7 +279,10 @@ def save_validation_outputs(base_exp_dir, outputs, inputs, tag, image_tag=None, 
     the mask half's result).
     outputs["vertex_normals"] / ["vertex_colors"] (validate's mesh_attributes), where present, follow the mesh: through the cleaning's
     vertex index, the normals through transform_normals; colours of vertices no source view sees (outputs["vertex_seen"] False: the network's
-    output is arbitrary there) are written mid-grey (128, 128, 128)."""
+    output is arbitrary there) are written mid-grey (128, 128, 128).
+    outputs["surface_depth"] / ["surface_normal_img"] / ["surface_img"] (validate's surface_render), where present, are written under
+    val_surface_depth/, val_surface_normal/ and val_surface_img/ by the writers of their volume-rendered counterparts; pixels whose ray did
+    not hit the surface are black."""
     if clean_frustum and not clean:
         raise ValueError("save_validation_outputs: clean_frustum=True needs clean=True")
     scene = inputs["scene"]
@@ -310,4 +313,14 @@ def save_validation_outputs(base_exp_dir, outputs, inputs, tag, image_tag=None, 
     save_depth(outputs["render_depth"], paths["render_depth"])
     paths["sdf_depth"] = os.path.join(base_exp_dir, "val_sdf_depth", f"{image_tag}_{tag}.png")
     save_depth(outputs["sdf_depth"], paths["sdf_depth"])
+    for key, sub, name in (("surface_depth", "val_surface_depth", "surface_depth"), ("surface_normal_img", "val_surface_normal", "surface_normal"),
+                           ("surface_img", "val_surface_img", "surface_img")):
+        if key not in outputs:
+            continue
+        os.makedirs(os.path.join(base_exp_dir, sub), exist_ok=True)
+        paths[name] = os.path.join(base_exp_dir, sub, f"{image_tag}_{tag}.png")
+        rgb = depth_to_rgb(outputs[key]) if key == "surface_depth" else np.asarray(outputs[key]).astype(np.uint8)
+        if outputs.get("surface_hit") is not None:        # (the colour map's lowest entry is not quite black)
+            rgb = np.where(np.asarray(outputs["surface_hit"], dtype=bool)[:, :, None], rgb, np.uint8(0))
+        Image.fromarray(rgb).save(paths[name])
     return paths

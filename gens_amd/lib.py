@@ -59,6 +59,15 @@ class PointGridArgs(C.Structure):      # gens_point_grid (K24)
         (n, _d) for n in ("lo_x", "lo_y", "lo_z", "cell")] + [(n, _i) for n in ("nx", "ny", "nz")]
 
 
+class TraceState(C.Structure):        # gens_trace_state (K31)
+    _fields_ = [(n, _p) for n in ("rays_o", "rays_d", "t", "t_lo", "t_hi", "g_lo", "g_hi", "t_end", "dlen", "status", "steps", "points", "live")] + [("n", _l)]
+
+
+class SurfacePackArgs(C.Structure):   # gens_surface_pack_args (K31)
+    _fields_ = [("grad", _p), ("color", _p), ("vis", _p), ("n_src", _i), ("idx", _p), ("m", _l), ("n", _l)] + [
+        (n, _p) for n in ("status", "t", "rays_d", "rot", "depth", "normal", "normal_img", "img", "seen", "hit")]
+
+
 # name -> argtypes, mirroring include/gens_hip.h declaration by declaration
 SIGNATURES = {
     "gens_pack_nchw": [_p, _p, _i, _i, _i, _i, _p],
@@ -210,6 +219,11 @@ SIGNATURES = {
     "gens_brick_mc_emit": [_p, _p, _p, _p, _i, _i, _p, _l, _f, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p],
     "gens_vertex_points": [_p, _l, _i, _d, _d, _d, _d, _d, _d, _p, _p],
     "gens_vertex_pack": [_p, _p, _p, _i, _l, _p, _p, _p, _p],
+    "gens_trace_begin": [C.POINTER(TraceState), _p, _p, _i, _fp, _fp, _p],
+    "gens_trace_march": [C.POINTER(TraceState), _p, _p, _l, _f, _f, _f, _i, _p],
+    "gens_trace_refine": [C.POINTER(TraceState), _p, _p, _l, _f, _i, _p],
+    "gens_trace_gather": [_p, _p, _l, _l, _p, _p],
+    "gens_surface_pack": [C.POINTER(SurfacePackArgs), _p],
 }
 
 _lib = None

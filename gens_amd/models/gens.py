@@ -100,6 +100,9 @@ class GenS(nn.Module):
         attrs = confs.get("mesh_attributes", None)              # optional: per-vertex "normals" / "colors" on extracted meshes (K30); a name or a list
         if attrs is not None:
             self.implicit_surface.mesh_attributes = (attrs,) if isinstance(attrs, str) else tuple(attrs)
+        surface = confs.get("surface_render", None)             # optional: validate also traces its rays to the surface (render_surface, K31); True or its keywords
+        if surface is not None:
+            self.implicit_surface.surface_render = dict(surface) if hasattr(surface, "keys") else bool(surface)
         lipschitz = confs.get("lattice_lipschitz", None)        # optional: the bound that lattice assumes (ImplicitSurface.lattice_lipschitz)
         if lipschitz is not None:
             self.implicit_surface.lattice_lipschitz = float(lipschitz)

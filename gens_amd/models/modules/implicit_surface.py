@@ -744,28 +744,14 @@ class ImplicitSurface(nn.Module):
         vols = volumes if isinstance(volumes, ops.VolumeSet) else ops.VolumeSet.packed(volumes)
         dev = vols.tensors[0].device
         pts = torch.as_tensor(points).detach().reshape(-1, 3).to(device=dev, dtype=torch.float32).contiguous()
-        n, chunk = pts.shape[0], max(1, int(chunk))
+        n = pts.shape[0]
         want_n, want_c = "normals" in names, "colors" in names
-        if want_n and self._fused_plan(vols) is None:      # (what _attribute_request could not see before the volumes were packed)
-            raise ValueError("mesh attributes: the normals need the fused SDF kernels; these volumes do not take them")
-        bplan = self._fused_blend_plan(views) if want_c else None
         normals = torch.empty(n, 3, device=dev, dtype=torch.float32) if want_n else None
         colors = torch.empty(n, 3, device=dev, dtype=torch.uint8) if want_c else None
         seen = torch.empty(n, device=dev, dtype=torch.uint8) if want_c else None
-
-        def run(evaluate):
-            for s in range(0, n, chunk):
-                e = min(s + chunk, n)
-                grad = evaluate(pts[s:e])[1] if want_n else None
-                rgb, vis = ops.blend_views(bplan, views, pts[s:e]) if want_c else (None, None)
-                ops.vertex_pack(grad, rgb, vis, normals=normals[s:e] if want_n else None, colors=colors[s:e] if want_c else None,
-                                seen=seen[s:e] if want_c else None)
-
-        if n and names:
-            if want_n:
-                self._lattice_passes(vols, None, run, want_grad=True)
-            else:
-                run(None)
+        if names:
+            self._point_chain(pts, vols, views, want_n, want_c, chunk, lambda s, e, grad, rgb, vis: ops.vertex_pack(
+                grad, rgb, vis, normals=normals[s:e] if want_n else None, colors=colors[s:e] if want_c else None, seen=seen[s:e] if want_c else None))
         out = {}
         if want_n:
             out["normals"] = normals.cpu().numpy()
@@ -773,6 +759,111 @@ class ImplicitSurface(nn.Module):
             out["colors"] = colors.cpu().numpy()
             out["seen"] = seen.cpu().numpy().astype(bool)
         return out
+
+    def _point_chain(self, pts, vols, views, want_n, want_c, chunk, sink):
+        """The network chain of vertex_attributes and render_surface on device points (n, 3) float32, `chunk` at a time:
+        ops.sdf_mlp(want_grad=True) (want_n) and ops.blend_views (want_c), then sink(s, e, grad, rgb, vis) for the rows s .. e - 1 (None for
+        what was not asked for).  The evaluator is _lattice_passes': a split-half overflow repeats the whole pass, sinks included, in float32."""
+        n, chunk = pts.shape[0], max(1, int(chunk))
+        if want_n and self._fused_plan(vols) is None:      # (what _attribute_request could not see before the volumes were packed)
+            raise ValueError("mesh attributes: the normals need the fused SDF kernels; these volumes do not take them")
+        bplan = self._fused_blend_plan(views) if want_c else None
+
+        def run(evaluate):
+            for s in range(0, n, chunk):
+                e = min(s + chunk, n)
+                grad = evaluate(pts[s:e])[1] if want_n else None
+                rgb, vis = ops.blend_views(bplan, views, pts[s:e]) if want_c else (None, None)
+                sink(s, e, grad, rgb, vis)
+
+        if n and (want_n or want_c):
+            if want_n:
+                self._lattice_passes(vols, None, run, want_grad=True)
+            else:
+                run(None)
+
+    surface_render = None          # validate also traces its rays to the surface (render_surface, K31) and returns surface_depth, surface_normal_img,
+                                   # surface_img and surface_hit.  None / False: off; True: every output; or a dict of render_surface's keywords
+                                   # (outputs, resolution, lipschitz, min_step, max_steps, refine) (DESIGN.md, section 5h)
+    last_surface_stats = None      # ops.sphere_trace's stats of the last render_surface call
+    SURFACE_OUTPUTS = ("depth", "normals", "colors")
+
+    def _surface_request(self, outputs, volumes, views, resolution, lipschitz, min_step, max_steps, refine, bound_min, bound_max):
+        """render_surface's arguments, checked before anything is launched -> (outputs in the order of SURFACE_OUTPUTS, lipschitz, min_step,
+        max_steps, refine).  The limits of the normals and colours are _attribute_request's."""
+        names = (outputs,) if isinstance(outputs, str) else tuple(outputs)
+        unknown = [a for a in names if a not in self.SURFACE_OUTPUTS]
+        if unknown:
+            raise ValueError(f"surface outputs {unknown!r}: the known ones are {self.SURFACE_OUTPUTS!r}")
+        names = tuple(a for a in self.SURFACE_OUTPUTS if a in names)
+        if not names:
+            raise ValueError(f"surface outputs: at least one of {self.SURFACE_OUTPUTS!r}")
+        self._attribute_request(("normals",) + tuple(a for a in names if a == "colors"), volumes, views)     # (the trace itself needs the fused SDF plan)
+        lipschitz = float(self.lattice_lipschitz if lipschitz is None else lipschitz)
+        if not lipschitz > 0.0 or lipschitz == float("inf"):
+            raise ValueError(f"render_surface: lipschitz = {lipschitz!r}, a positive finite bound")
+        if min_step is None:
+            if int(resolution) < 2:
+                raise ValueError(f"render_surface: resolution = {resolution}, at least 2 points per axis")
+            lo, hi = bound_min.tolist(), bound_max.tolist()
+            min_step = min((float(b) - float(a)) / (int(resolution) - 1) for a, b in zip(lo, hi))
+        min_step = float(min_step)
+        if not min_step > 0.0 or min_step == float("inf"):
+            raise ValueError(f"render_surface: min_step = {min_step!r}, a positive finite length")
+        if int(max_steps) < 1:
+            raise ValueError(f"render_surface: max_steps = {max_steps}, at least 1")
+        if int(refine) < 0:
+            raise ValueError(f"render_surface: refine = {refine}, at least 0")
+        return names, lipschitz, min_step, int(max_steps), int(refine)
+
+    @torch.no_grad()
+    def render_surface(self, rays_o, rays_d, near, far, volumes, bound_min, bound_max, c2ws, views=None, outputs=("depth", "normals", "colors"),
+                       resolution=512, threshold=0.0, chunk=1 << 21, lipschitz=None, min_step=None, max_steps=256, refine=2, hw=None):
+        """The surface sdf + threshold = 0 as the rays see it, by sphere tracing (ops.sphere_trace, K31): per ray one
+        value evaluation per march round while it is LIVE, `refine` more on its bracket, and at a hit one value + gradient and one blend
+        evaluation -- validate's volume rendering takes 128 of each.  rays_o / rays_d (n, 3) or (H, W, 3), near / far (one value or one per
+        ray), bound_min / bound_max: device tensors; c2ws: the scene's poses (rot = inverse(c2ws[0][:3,:3]), the rotation validate's normal
+        image uses); views: the scene's ops.SceneViews, needed for "colors".
+        lipschitz (default: the attribute `lattice_lipschitz`): the assumed bound on |d sdf| per unit length, the heuristic of the sparse
+        lattice -- a steeper field can be stepped through.  min_step (default: the smallest spacing of a `resolution`-point lattice over the
+        box, so the map is bracketed as finely as that mesh's cells): a sheet thinner than it can be stepped over.
+        -> dict of host arrays shaped (H, W, ...) by hw or the rays' own leading shape, else flat:
+            "t", "status" (uint8, ops.TRACE_*), "steps", "hit" (bool)   always;
+            "depth" float32: t (rot d)_z at a hit, else 0;
+            "normal" (.., 3) float32 unit grad sdf and "normal_img" (.., 3) float32 in validate's normal_img convention ("normals");
+            "img" (.., 3) uint8 in validate's img_fine convention and "seen" bool ("colors").  Everything is 0 where the ray is not a hit.
+        INSIDE and EXHAUSTED rays are counted in self.last_surface_stats (ops.sphere_trace's stats), not hidden.  The evaluator is the
+        lattice's (_lattice_passes): this scene's sdf_precision, and a split-half overflow repeats the whole trace in float32; no mask
+        volume is consulted.  ValueError before any launch for what _attribute_request refuses and for a bad lipschitz / min_step / max_steps."""
+        names, lipschitz, min_step, max_steps, refine = self._surface_request(outputs, volumes, views, resolution, lipschitz, min_step, max_steps,
+                                                                              refine, bound_min, bound_max)
+        vols = volumes if isinstance(volumes, ops.VolumeSet) else ops.VolumeSet.packed(volumes)
+        shape = tuple(int(v) for v in hw) if hw is not None else tuple(rays_o.shape[:-1])
+        o, d = rays_o.reshape(-1, 3), rays_d.reshape(-1, 3)
+        lo, hi = bound_min.tolist(), bound_max.tolist()
+        traced, stats = self._lattice_passes(vols, None, lambda evaluate: ops.trace_rays(
+            evaluate, o, d, near, far, lo, hi, lipschitz, min_step, max_steps, refine, threshold, chunk))
+        self.last_surface_stats = stats
+        want_n, want_c = "normals" in names, "colors" in names
+        # the nine floats validate's normal image uses, from the same set-up launch (the rotation does not depend on the intrinsics: unit ones)
+        rot = ops.SceneCams(torch.eye(4, device=c2ws.device).expand(c2ws.shape[0], 4, 4).contiguous(), c2ws).rot_inv
+        packed = ops.surface_pack(traced["status"], traced["t"], d, rot)
+        if (want_n or want_c) and stats["hit"]:
+            hits = ops.compact_valid(traced["status"] == ops.TRACE_HIT)[0][:stats["hit"]]
+            pts = ops.trace_gather(traced["points"], hits, stats["hit"])
+            self._point_chain(pts, vols, views, want_n, want_c, chunk, lambda s, e, grad, rgb, vis: ops.surface_pack(
+                traced["status"], traced["t"], d, rot, grad, rgb, vis, index=hits[s:e], out=packed))
+        n = o.shape[0]
+        out = {"t": traced["t"], "status": traced["status"], "steps": traced["steps"], "hit": packed["hit"].bool(), "depth": packed["depth"]}
+        if want_n:
+            out["normal"] = packed.get("normal", torch.zeros(n, 3, device=o.device))
+            out["normal_img"] = packed.get("normal_img", torch.zeros(n, 3, device=o.device))
+        if want_c:
+            out["img"] = packed.get("img", torch.zeros(n, 3, device=o.device, dtype=torch.uint8))
+            out["seen"] = packed.get("seen", torch.zeros(n, device=o.device, dtype=torch.uint8)).bool()
+        if "depth" not in names:
+            del out["depth"]
+        return {k: v.cpu().numpy().reshape(shape + tuple(v.shape[1:])) for k, v in out.items()}
 
     def extract_geometry(self, volumes, bound_min, bound_max, resolution, threshold, shard=None, sparse=None, sparse_mesh=None, attributes=None,
                          views=None):
@@ -814,14 +905,22 @@ class ImplicitSurface(nn.Module):
     @torch.no_grad()
     def validate(self, rays_o, rays_d, near, far, volumes, mask_volumes, imgs, features, match_features, intrs, c2ws, bound_min, bound_max,
                  hw, cos_anneal_ratio=1.0, step=None, extract_geometry=True, mesh_resolution=512, threshold=0.0, scene=None, shard=None, sparse=None,
-                 sparse_mesh=None, mesh_attributes=None):
+                 sparse_mesh=None, mesh_attributes=None, surface_render=None):
         """shard (gens_amd.distributed.Shard, optional): render only this rank's contiguous ray range and evaluate only its lattice
         chunks; the (P, 8) image buffer / the lattice slabs are gathered over RCCL, so every rank returns the whole image.  The jitter
         of EVERY ray is drawn on every rank from the identically seeded CPU generator (the reference's draw order) and sliced with
         the rays: the image does not depend on the partition.  sparse, sparse_mesh: extract_geometry's options (the two-level lattice, marching cubes
         on its bricks).  mesh_attributes: extract_geometry's `attributes` with this scene's views -> outputs["vertex_normals"],
-        ["vertex_colors"], ["vertex_seen"] beside the mesh."""
+        ["vertex_colors"], ["vertex_seen"] beside the mesh.  surface_render (default: the attribute of that name, None / False = off; True, or
+        a dict of render_surface's keywords): the rays of this image are also traced to the surface (render_surface, K31) ->
+        outputs["surface_depth"], ["surface_normal_img"], ["surface_img"], ["surface_hit"]; not with a shard."""
         outputs = {}
+        surface_render = self.surface_render if surface_render is None else surface_render
+        if surface_render:
+            if shard is not None:
+                raise ValueError("surface_render is not sharded: trace the rays on one rank (render_surface)")
+            surface_kw = {"resolution": mesh_resolution, **(surface_render if isinstance(surface_render, dict) else {})}
+            surface_kw["outputs"] = self.SURFACE_OUTPUTS
         if scene is None:
             scene = Scene(volumes, mask_volumes, imgs, features, match_features, intrs, c2ws)
         height, width = int(hw[0]), int(hw[1])
@@ -908,6 +1007,11 @@ class ImplicitSurface(nn.Module):
         outputs["sdf_depth"] = flat[9 * p_:10 * p_].reshape([height, width])
         outputs["render_depth"] = flat[10 * p_:11 * p_].reshape([height, width])
         self.last_render_s = _time.perf_counter() - t_render
+        if surface_render:
+            surf = self.render_surface(rays_o, rays_d, near.to(rays_o.device), far.to(rays_o.device), scene.volumes_nograd(), bound_min, bound_max, c2ws, views=scene.views,
+                                       threshold=threshold, hw=(height, width), **surface_kw)
+            outputs["surface_depth"], outputs["surface_normal_img"] = surf["depth"], surf["normal_img"]
+            outputs["surface_img"], outputs["surface_hit"] = surf["img"], surf["hit"]
         return outputs
 
     def val_chunk_for(self, n_rays):

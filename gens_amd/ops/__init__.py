@@ -25,6 +25,7 @@ is what it was when ops was one module:
                   shares with it: dimensions, point and classify launches under either set of limits, the front end of both.
     ops.brick_mcubes  K29: marching cubes on that lattice's bricks, without the dense lattice (brick_marching_cubes).
     ops.vertex_attrs  K30: per-vertex attributes of an extracted mesh: lattice vertices to points, gradient / colour to normals / 8-bit colours.
+    ops.trace     K31: sphere tracing of the surface along rays (sphere_trace) and the per-ray depth / normal / colour pack (surface_pack).
 """
 from .base import *  # noqa: F401,F403
 from .volume import *  # noqa: F401,F403
@@ -42,3 +43,4 @@ from .filter import *  # noqa: F401,F403
 from .lattice import *  # noqa: F401,F403
 from .brick_mcubes import *  # noqa: F401,F403
 from .vertex_attrs import *  # noqa: F401,F403
+from .trace import *  # noqa: F401,F403

@@ -62,7 +62,8 @@ const char* gens_last_error(void);
  *       and K27's gens_largest_component, gens_components_scratch_bytes, gens_unpack_mask_bits, and K28's gens_sparse_coarse_points,
  *       gens_sparse_classify, gens_sparse_brick_points, gens_sparse_fill, gens_sparse_scatter, gens_sparse_leaks, and K29's
  *       gens_brick_coarse_points, gens_brick_points, gens_brick_active, gens_brick_emit_flags, gens_brick_mc_classify, gens_brick_mc_emit,
- *       and K30's gens_vertex_points, gens_vertex_pack. */
+ *       and K30's gens_vertex_points, gens_vertex_pack, and K31's gens_trace_begin, gens_trace_march, gens_trace_refine, gens_trace_gather,
+ *       gens_surface_pack. */
 int gens_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -927,6 +928,83 @@ int gens_vertex_points(const double* vertices, int64_t n, int resolution, double
                        double lo_y, double lo_z, float* points, void* stream);
 int gens_vertex_pack(const float* grad, const float* color, const uint8_t* vis, int n_src, int64_t n, float* normals, uint8_t* colors,
                      uint8_t* seen, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * K31  Sphere tracing of the surface along rays (ops.sphere_trace, ImplicitSurface.render_surface), csrc/k31_surface_trace.hip: the
+ *      streaming launches between the network evaluations.  tests/surface_trace_reference.py restates all of it in numpy.
+ *
+ *   Definition.  g(p) = sdf(p) + threshold; the surface is g = 0; g > 0 is the side K12 calls u < iso (u = -sdf), g <= 0 the other side
+ *   (-0.0 counts as 0).  A ray is p(t) = o + t d in float32; d need not be unit and t counts in units of d, like z_vals.  Parameters:
+ *   lipschitz L > 0 (an assumed bound on |d sdf| per unit length -- the heuristic of the sparse lattice), min_step > 0 in
+ *   world units, max_steps >= 1, refine >= 0.  Per ray: float32 t, t_lo, t_hi, g_lo, g_hi, t_end, |d|; a one-byte status; a step count.
+ *   Every float32 operation below is rounded on its own, in the order written; points handed to the evaluator are o + t * d, un-fused.
+ *     Begin.  Slab test against [lo, hi] intersected with [near, far]: per axis (lo - o) / d and (hi - o) / d, ordered; an axis with d = 0
+ *       contributes (-inf, +inf) if lo <= o <= hi and otherwise the ray misses.  t0 = max(near, entries), t_end = min(far, exits).
+ *       Non-finite o or d: BAD.  |d| = 0 or not t0 < t_end: MISS.  Else LIVE at t = t0.  |d| = sqrt((dx^2 + dy^2) + dz^2) in float64 from the
+ *       float32 components, rounded once.
+ *     March.  One round evaluates g at p(t) for every LIVE ray (its evaluation number k = steps + 1):
+ *       g not finite                 BAD
+ *       g <= 0 and k == 1            INSIDE (the ray enters the box below the surface: not a hit, the mesh is open there too)
+ *       g <= 0 later                 BRACKET, (t_hi, g_hi) = (t, g); (t_lo, g_lo) is the previous round's
+ *       g > 0 and t == t_end         MISS (the exit point itself was sampled)
+ *       g > 0 and k == max_steps     EXHAUSTED
+ *       g > 0 otherwise              (t_lo, g_lo) = (t, g); t = min(t + max(g / L, min_step) / |d|, t_end)
+ *     Refine.  `refine` rounds on the BRACKET rays: g at t_m = 0.5 (t_lo + t_hi); g <= 0 replaces the hi end, anything else the lo end.
+ *       Then t = t_lo + (t_hi - t_lo) (g_lo / (g_lo - g_hi)) and the status is HIT: marching cubes' own rule on a crossing edge, on a
+ *       segment of at most min_step 2^-refine.
+ *     Pack, per ray, with rot = inverse(c2ws[0][:3,:3]) (9 floats on the device, row-major) and rot v = (v0 rot[k][0] + v1 rot[k][1]) +
+ *       v2 rot[k][2]: depth = t (rot d)_z for HIT and 0 otherwise (the reference's z_val * cos, implicit_surface.py:298); normal = K30's unit
+ *       normal of the gradient at the hit point; normal_img = min(max((rot normal) 128 + 128, 0), 255) in float32; img = K30's 8-bit
+ *       colour; seen = K30's; hit = (status == HIT).  Everything is 0 where the ray is not a hit.
+ *
+ *   gens_trace_state: the rays (rays_o, rays_d (n, 3)) and the per-ray state on the device; `points` (n, 3) holds the NEXT point of every ray
+ *     that needs an evaluation (a LIVE ray's p(t), a BRACKET ray's p(t_m)) and, after the final refine round, the hit point; `live` (n) is 1
+ *     for LIVE rays (what gens_compact_valid takes); t of a BRACKET ray is t_m.  steps counts the march evaluations.
+ *   gens_trace_begin: near / far: one float each (per_ray = 0) or (n) (per_ray = 1) on the device; lo / hi: 3 HOST floats each.  Writes all
+ *     of the state (rays that are not LIVE: t = t_end = 0, point 0).
+ *   gens_trace_march: sdf (m): the evaluator's values at the points of the rays idx[0 .. m) (int64, device; NULL: rays 0 .. m - 1).  Entries
+ *     outside 0 .. n - 1 and rays that are not LIVE are left alone.
+ *   gens_trace_refine: the same for BRACKET rays; sdf == NULL skips the bisection (refine = 0: final only); final != 0 interpolates and
+ *     sets HIT, else the next mid-point is written.
+ *   gens_trace_gather: out (m, 3) = points[idx[j]] (rows outside 0 .. n - 1: zeros).
+ *   gens_surface_pack: rows j < m of grad / color / vis (n_src flags per row) belong to ray idx[j] (NULL: ray j); status, t, rays_d and the
+ *     outputs are per ray (n).  Any output pointer may be NULL (not written); grad == NULL: no normals; color == NULL: no img / seen.
+ *   Arguments are checked before any launch: null pointers, negative counts, lipschitz / min_step not positive and finite, max_steps < 1,
+ *   n_src outside 1 .. 255: GENS_EINVAL; n or m >= 2^31 (gather: 3 m): GENS_ELIMIT.  n == 0 / m == 0 succeed without a launch.  ABI stays 12.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define GENS_TRACE_LIVE 0
+#define GENS_TRACE_HIT 1
+#define GENS_TRACE_MISS 2
+#define GENS_TRACE_INSIDE 3
+#define GENS_TRACE_EXHAUSTED 4
+#define GENS_TRACE_BAD 5
+#define GENS_TRACE_BRACKET 6
+typedef struct {
+    const float *rays_o, *rays_d;
+    float *t, *t_lo, *t_hi, *g_lo, *g_hi, *t_end, *dlen;
+    uint8_t* status;
+    int32_t* steps;
+    float* points;
+    uint8_t* live;
+    int64_t n;
+} gens_trace_state;
+typedef struct {
+    const float *grad, *color;
+    const uint8_t* vis;
+    int n_src;
+    const int64_t* idx;
+    int64_t m, n;
+    const uint8_t* status;
+    const float *t, *rays_d, *rot;
+    float *depth, *normal, *normal_img;
+    uint8_t *img, *seen, *hit;
+} gens_surface_pack_args;
+int gens_trace_begin(const gens_trace_state* s, const float* near, const float* far, int per_ray, const float* lo, const float* hi, void* stream);
+int gens_trace_march(const gens_trace_state* s, const float* sdf, const int64_t* idx, int64_t m, float threshold, float lipschitz,
+                     float min_step, int max_steps, void* stream);
+int gens_trace_refine(const gens_trace_state* s, const float* sdf, const int64_t* idx, int64_t m, float threshold, int final, void* stream);
+int gens_trace_gather(const float* points, const int64_t* idx, int64_t m, int64_t n, float* out, void* stream);
+int gens_surface_pack(const gens_surface_pack_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K14  C (m x n) = A^T B for tall row-major operands A (k x m), B (k x n), k >> m, n: the weight-gradient product of the training
