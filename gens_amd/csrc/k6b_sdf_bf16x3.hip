@@ -15,6 +15,9 @@
 //     ring of four 8 KB chunks filled three chunks ahead.
 //   * the value kernel is the forward half of the same code (GRAD = false) reading the forward prefix of the same stream: the two kernels
 //     issue the same MFMAs in the same order on the same operands, so they return the SAME float32 sdf for the same point.
+//   * at three levels the value kernel is built for TWO waves per SIMD (two workgroups per CU, each with its own ring): one wave's MFMAs
+//     issue while the other does its softplus and split, which a single wave between its sched_barrier fences cannot overlap.  That takes
+//     <= 256 registers without scratch (a spill would also count in the vmcnt of the chunk boundaries): see DIET in the kernel.
 //   * softplus and softplus' (float32), the trilinear look-up and its Jacobians, the stash of layer 2's softplus' and the chain rule to x
 //     are k6gh's; the gradients need no scaling (bf16 has float32's range).
 #include "common.h"
@@ -28,7 +31,13 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 #define GB_TERMS SPLIT3_TERMS               // pieces per (K block, output tile): x0, x1, x2 (split3.h)
 #define GB_CH 8                             // pieces per chunk of the ring
 #define GB_RING 4
-#define GB_GT 2                             // output tiles per group of A operands
+#define GB_GT 2                             // output tiles per group of A operands (the two-wave build: one)
+// resident waves per SIMD: two for the value kernel at three levels, on half the register file (the "diet" in the kernel); the gradient
+// kernels (160 KB of LDS) and the five-level value kernel (28 more conditioning registers) stay at one
+#define GB_OCC(NLEV_, GRAD_) (!(GRAD_) && (NLEV_) == 3 ? 2 : 1)
+#define GB_NCL 2                            // the two-wave build: conditioning K blocks that wait in LDS between the layers
+#define GB_CL_BYTES (GB_NCL * GB_TERMS * GB_PIECE)      // ... per wave, behind the ring
+#define GB_VALUE_LDS_BYTES(NLEV_) (GB_W_BYTES + (GB_OCC(NLEV_, false) == 2 ? GB_WAVES * GB_CL_BYTES : 0))
 #define GB_LPW (GB_CH / GB_WAVES)           // LDS-direct loads per wave and chunk
 #define GB_W_BYTES (GB_RING * GB_CH * GB_PIECE)
 #define GB_D_BYTES (2 * 16 * 64 * 16)       // softplus' of layers 0 and 1 of one wave
@@ -43,6 +52,32 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
     {                                                                       \
         const Split3Word sw__ = split3_pair((A_), (B_));                    \
         _Pragma("unroll") for (int k__ = 0; k__ < GB_TERMS; ++k__) (BLK_).p[k__][(W_)] = sw__.w[k__]; \
+    }
+
+// The point encoding of this lane as B-operand blocks.  Expands inside sdf_bf16x3_k and reads its locals x[3] (the point), scale and half
+// (the lane's half of the K slots); with ONLY_ = -1 it also adds the three inputs to the kernel's nan_sum.  Two modes:
+//   ONLY_ = -1    both K blocks -> P_[0], P_[1]                   (the prologue of every build)
+//   ONLY_ = 0, 1  that K block alone -> P_[0], nan_sum untouched  (the two-wave build at layer 3, which encodes x again)
+// A macro and not a function: as a lambda the one-wave builds no longer compiled to the instructions they had.
+#define GB_ENCODE_POINT(P_, ONLY_)                                          \
+    {                                                                       \
+        float qe_[16];                                                      \
+        _Pragma("unroll") for (int ke_ = 0; ke_ < 16; ++ke_) qe_[ke_] = 0.0f; \
+        _Pragma("unroll") for (int ae_ = 0; ae_ < 3; ++ae_) {               \
+            const float v = x[ae_] * scale;                                 \
+            float s0, c0, s1, c1;                                           \
+            hw_sincos(v * (half ? 4.0f : 1.0f), s0, c0);                    \
+            hw_sincos(v * (half ? 8.0f : 2.0f), s1, c1);                    \
+            if (half == 0) {                                                \
+                qe_[ae_] = v; qe_[3 + ae_] = s0; qe_[6 + ae_] = c0; qe_[9 + ae_] = s1; qe_[12 + ae_] = c1; \
+            } else {                                                        \
+                qe_[ae_] = s0; qe_[3 + ae_] = c0; qe_[6 + ae_] = s1; qe_[9 + ae_] = c1; \
+            }                                                               \
+            if ((ONLY_) < 0) nan_sum += x[ae_];                             \
+        }                                                                   \
+        if (half == 0) qe_[15] = 1.0f;                                      \
+        _Pragma("unroll") for (int ke_ = 0; ke_ < 16; ke_ += 2)             \
+            if ((ONLY_) < 0 || (ONLY_) == (ke_ >> 3)) GB_PUT((P_)[(ONLY_) < 0 ? ke_ >> 3 : 0], (ke_ & 7) >> 1, qe_[ke_], qe_[ke_ + 1]) \
     }
 
 // value of one packed (X, Y, Z, 4) volume at x and its derivative with respect to x (zero padding, align_corners=True)
@@ -108,7 +143,7 @@ struct GradShapeB {
 };
 
 template <int NLEV, bool GRAD>
-__global__ __launch_bounds__(64 * GB_WAVES, 1) void sdf_bf16x3_k(LevelSet vols, const char* __restrict__ pieces, const float* w_out, float b_last,
+__global__ __launch_bounds__(64 * GB_WAVES, GB_OCC(NLEV, GRAD)) void sdf_bf16x3_k(LevelSet vols, const char* __restrict__ pieces, const float* w_out, float b_last,
                                                                  float scale, float inv_scale, const float* __restrict__ pts,
                                                                  const int64_t* __restrict__ index, int64_t n_max, const int32_t* __restrict__ n_dev,
                                                                  float* __restrict__ sdf_out, float* __restrict__ grad_out,
@@ -116,6 +151,11 @@ __global__ __launch_bounds__(64 * GB_WAVES, 1) void sdf_bf16x3_k(LevelSet vols, 
     typedef GradShapeB<NLEV> S;
     constexpr int NCH = S::NCH, NC = S::NC, TC = S::TC, MID = NLEV / 2;
     constexpr int NCHUNK = GRAD ? S::NCHUNK : S::NCHUNK_FWD;
+    // DIET: the build for two waves per SIMD, <= 256 registers: A operands one tile ahead (GT = 1), the point encoded again at layer 3 and
+    // the last GB_NCL conditioning blocks read back from LDS at every layer; the MFMAs, their operands and their order per accumulator are
+    // those of the one-wave build
+    constexpr bool DIET = GB_OCC(NLEV, GRAD) == 2;
+    constexpr int GT = DIET ? 1 : GB_GT;
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -167,27 +207,7 @@ __global__ __launch_bounds__(64 * GB_WAVES, 1) void sdf_bf16x3_k(LevelSet vols, 
     float nan_sum = 0.0f;      // not-a-number inputs must come out as not-a-number: see the poison term below
 
     Split3Block P[2];     // point encoding: half 0 = x, octaves 0 and 1, ONE; half 1 = octaves 2 and 3, zeros
-    {
-        float q[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) q[k] = 0.0f;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float v = x[a] * scale;
-            float s0, c0, s1, c1;
-            hw_sincos(v * (half ? 4.0f : 1.0f), s0, c0);
-            hw_sincos(v * (half ? 8.0f : 2.0f), s1, c1);
-            if (half == 0) {
-                q[a] = v; q[3 + a] = s0; q[6 + a] = c0; q[9 + a] = s1; q[12 + a] = c1;
-            } else {
-                q[a] = s0; q[3 + a] = c0; q[6 + a] = s1; q[9 + a] = c1;
-            }
-            nan_sum += x[a];
-        }
-        if (half == 0) q[15] = 1.0f;
-#pragma unroll
-        for (int k = 0; k < 16; k += 2) GB_PUT(P[k >> 3], (k & 7) >> 1, q[k], q[k + 1])
-    }
+    GB_ENCODE_POINT(P, -1)
 
     Split3Block C[NC];    // volume features: 5 encodings of this half's NCH channels, then ONE (half 0), then zeros
     const float* wo = w_out + half * (64 + 16 * TC);
@@ -228,15 +248,28 @@ __global__ __launch_bounds__(64 * GB_WAVES, 1) void sdf_bf16x3_k(LevelSet vols, 
 #pragma unroll
             for (int q = 0; q < 5; ++q) s_cond = __builtin_fmaf(e[5 * j + q], wo[64 + 5 * j + q], s_cond);       // layer 6 reads the conditioning features too
         }
+        if constexpr (DIET) {      // finished HERE: left to itself the compiler sinks the two sums to layer 3 and carries e[] and w_out to them
+            asm volatile("" : "+v"(s_cond));
+            asm volatile("" : "+v"(nan_sum));
+        }
 #pragma unroll
         for (int k = 0; k < 8 * NC; k += 2) GB_PUT(C[k >> 3], (k & 7) >> 1, e[k], e[k + 1])
+    }
+
+    // [block][term][lane], this wave's own; the other builds allocate no such area and get no pointer to one
+    u32x4* const CL = DIET ? (u32x4*)(lds + GB_W_BYTES + wave * GB_CL_BYTES) : nullptr;
+    if constexpr (DIET) {
+#pragma unroll
+        for (int b = 0; b < GB_NCL; ++b)
+#pragma unroll
+            for (int k = 0; k < GB_TERMS; ++k) CL[(b * GB_TERMS + k) * 64 + lane] = C[NC - GB_NCL + b].p[k];
     }
 
     f32x16 acc[4];                 // the product being accumulated
     Split3Block H[8];              // the operand of the running product: activations, then G_l (block 2 t + (r >> 3), slot r & 7 <- tile t, register r)
     f32x16 D3[4], D4[4];           // softplus' of layers 3, 4 (GRAD)
     f32x16 gc[TC], gp;             // d sdf / d (this lane's conditioning slots), d sdf / d (its point-encoding slots)
-    u32x4 abuf[2][GB_TERMS * GB_GT];      // A operands: this group's and the next one's
+    u32x4 abuf[2][GB_TERMS * GT];      // A operands: this group's and the next one's
     int par = 0;                   // (compile-time after unrolling, like every index below)
     int dirty = GRAD ? 1 : 0;      // stores are outstanding: the next chunk boundary waits for everything
 
@@ -256,7 +289,7 @@ __global__ __launch_bounds__(64 * GB_WAVES, 1) void sdf_bf16x3_k(LevelSet vols, 
     }
     // pieces P0_ .. P0_ + CNT_ -> A register set SET_
 #define GB_LOAD(SET_, P0_, CNT_)                                                                         \
-    _Pragma("unroll") for (int j_ = 0; j_ < GB_TERMS * GB_GT; ++j_) if (j_ < (CNT_)) {                    \
+    _Pragma("unroll") for (int j_ = 0; j_ < GB_TERMS * GT; ++j_) if (j_ < (CNT_)) {                      \
         const int p_ = (P0_) + j_;                                                                       \
         if (p_ % GB_CH == 0) GB_BOUNDARY(p_ / GB_CH)                                                     \
         abuf[SET_][j_] = *((const u32x4*)(lds + ((p_ / GB_CH) % GB_RING) * (GB_CH * GB_PIECE) + (p_ % GB_CH) * GB_PIECE) + lane); \
@@ -266,21 +299,21 @@ __global__ __launch_bounds__(64 * GB_WAVES, 1) void sdf_bf16x3_k(LevelSet vols, 
 #define GB_RACC(T_) (*((T_) < 4 ? &acc[(T_) < 4 ? (T_) : 0] : (T_) < 4 + TC ? &gc[(T_) < 4 + TC && (T_) >= 4 ? (T_) - 4 : 0] : &gp))
     // the six products of one operand pair, smallest first: weight term WA_ x activation term WB_
 #define GB_TERM(WA_, WB_, REV_, B_)                                                                      \
-    _Pragma("unroll") for (int t_ = 0; t_ < GB_GT; ++t_) if (t_ < nt_) {                                 \
+    _Pragma("unroll") for (int t_ = 0; t_ < GT; ++t_) if (t_ < nt_) {                                    \
         if (REV_) GB_MFMA(GB_RACC(t0_ + t_), abuf[par][GB_TERMS * t_ + (WA_)], (B_)[i_].p[(WB_)]);       \
         else GB_MFMA(acc[(t0_ + t_) & 3], abuf[par][GB_TERMS * t_ + (WA_)], (B_)[i_].p[(WB_)]);          \
     }
     // CNT_ K blocks of NT_ output tiles from piece P0_ on, B operands B_[0 .. CNT_); REV_: the accumulators of a reverse block.  The A
-    // operands arrive in groups of GB_GT tiles (three terms each), one group ahead of the MFMAs that read them.  Within a group the
+    // operands arrive in groups of GT tiles (three terms each), one group ahead of the MFMAs that read them.  Within a group the
     // accumulators alternate.
 #define GB_SEGMENT(P0_, CNT_, NT_, B_, REV_)                                                             \
     {                                                                                                    \
-        constexpr int ng__ = ((NT_) + GB_GT - 1) / GB_GT;      /* (CNT_ and NT_ are constant expressions at every call) */ \
-        GB_LOAD(par, (P0_), GB_TERMS * ((NT_) < GB_GT ? (NT_) : GB_GT))                                  \
+        constexpr int ng__ = ((NT_) + GT - 1) / GT;      /* (CNT_ and NT_ are constant expressions at every call) */ \
+        GB_LOAD(par, (P0_), GB_TERMS * ((NT_) < GT ? (NT_) : GT))                                        \
         _Pragma("unroll") for (int q_ = 0; q_ < (CNT_) * ng__; ++q_) {                                   \
-            const int i_ = q_ / ng__, t0_ = (q_ % ng__) * GB_GT, nt_ = (NT_) - t0_ < GB_GT ? (NT_) - t0_ : GB_GT; \
+            const int i_ = q_ / ng__, t0_ = (q_ % ng__) * GT, nt_ = (NT_) - t0_ < GT ? (NT_) - t0_ : GT; \
             if (q_ + 1 < (CNT_) * ng__) {                                                                \
-                const int i2_ = (q_ + 1) / ng__, t2_ = ((q_ + 1) % ng__) * GB_GT, n2_ = (NT_) - t2_ < GB_GT ? (NT_) - t2_ : GB_GT; \
+                const int i2_ = (q_ + 1) / ng__, t2_ = ((q_ + 1) % ng__) * GT, n2_ = (NT_) - t2_ < GT ? (NT_) - t2_ : GT; \
                 GB_LOAD(par ^ 1, (P0_) + GB_TERMS * ((NT_) * i2_ + t2_), GB_TERMS * n2_)                  \
             }                                                                                            \
             __builtin_amdgcn_sched_barrier(0);                                                           \
@@ -317,8 +350,30 @@ __global__ __launch_bounds__(64 * GB_WAVES, 1) void sdf_bf16x3_k(LevelSet vols, 
     for (int l = 0; l < 6; ++l) {
         if (l > 0) {
             GB_ZERO();
+            if constexpr (DIET) {      // (opaque lane: a new address to the compiler, or it keeps the blocks of the layer before)
+                int lane_o = lane;
+                asm volatile("" : "+v"(lane_o));
+#pragma unroll
+                for (int b = 0; b < GB_NCL; ++b)
+#pragma unroll
+                    for (int k = 0; k < GB_TERMS; ++k) C[NC - GB_NCL + b].p[k] = CL[(b * GB_TERMS + k) * 64 + lane_o];
+            }
             GB_SEGMENT(S::fwd(l), NC, 4, C, false);
-            if (l == 3) GB_SEGMENT(S::fwd(3) + S::BLK * NC, 2, 4, P, false);
+            if (l == 3) {
+                if constexpr (!DIET) {
+                    GB_SEGMENT(S::fwd(3) + S::BLK * NC, 2, 4, P, false);
+                } else {
+                    // x is encoded again, one K block at a time (the same instructions on the same x: the same bits), instead of 24 registers
+                    // held from the prologue to here; opaque, or the compiler keeps the first copy
+#pragma unroll
+                    for (int pb = 0; pb < 2; ++pb) {
+#pragma unroll
+                        for (int a = 0; a < 3; ++a) asm volatile("" : "+v"(x[a]));
+                        GB_ENCODE_POINT(P, pb)
+                        GB_SEGMENT(S::fwd(3) + S::BLK * (NC + pb), 1, 4, P, false);
+                    }
+                }
+            }
             GB_SEGMENT(S::fwd(l) + S::BLK * (NC + (l == 3 ? 2 : 0)), 8, 4, H, false);
         }
 #pragma unroll
@@ -364,7 +419,14 @@ __global__ __launch_bounds__(64 * GB_WAVES, 1) void sdf_bf16x3_k(LevelSet vols, 
     s_val += __shfl_xor(s_val, 32, 64);
 
     if constexpr (!GRAD) {
-        if (half == 0 && live) sdf_out[src] = (s_val + b_last) * inv_scale;
+        if constexpr (!DIET) {
+            if (half == 0 && live) sdf_out[src] = (s_val + b_last) * inv_scale;
+        } else {      // the row is looked up again (opaque lane number), not carried in two registers through the layers
+            int lane_o = lane;
+            asm volatile("" : "+v"(lane_o));
+            const int64_t row_o = m0 + 32 * wave + (lane_o & 31);
+            if (lane_o < 32 && row_o < n) sdf_out[index ? index[row_o] : row_o] = (s_val + b_last) * inv_scale;
+        }
     } else {
         // ------------------------------------------------------------------ reverse pass
 #pragma unroll
@@ -499,6 +561,8 @@ extern "C" int gens_sdf_bf16x3_pieces(int n_levels) {
     return n_levels == 3 ? GradShapeB<3>::NCHUNK * GB_CH : n_levels == 5 ? GradShapeB<5>::NCHUNK * GB_CH : 0;
 }
 
+static GensLdsOptIn g_grad_lds3, g_grad_lds5;      // the gradient kernels' 160 KB of LDS, granted once per device
+
 extern "C" int64_t gens_sdf_grad_f16_stash_bytes(void);      // the stash is k6gh's: the same slots, the same layout
 
 static int check_bf16x3_args(const char* who, int n_levels, const void* pieces, const float* w_out, float scale, const float* pts, int64_t n,
@@ -520,10 +584,10 @@ extern "C" int gens_sdf_value_bf16x3(const float* const* vols_packed, const int*
     if (n == 0) return 0;
     const unsigned grid = gens_blocks(n, 32 * GB_WAVES);
     if (n_levels == 3)
-        sdf_bf16x3_k<3, false><<<grid, 64 * GB_WAVES, GB_W_BYTES, (hipStream_t)stream>>>(vs, (const char*)pieces, w_out, b_last, scale, 1.0f / scale, pts,
+        sdf_bf16x3_k<3, false><<<grid, 64 * GB_WAVES, GB_VALUE_LDS_BYTES(3), (hipStream_t)stream>>>(vs, (const char*)pieces, w_out, b_last, scale, 1.0f / scale, pts,
                                                                                           index, n, n_device, sdf_out, nullptr, nullptr);
     else
-        sdf_bf16x3_k<5, false><<<grid, 64 * GB_WAVES, GB_W_BYTES, (hipStream_t)stream>>>(vs, (const char*)pieces, w_out, b_last, scale, 1.0f / scale, pts,
+        sdf_bf16x3_k<5, false><<<grid, 64 * GB_WAVES, GB_VALUE_LDS_BYTES(5), (hipStream_t)stream>>>(vs, (const char*)pieces, w_out, b_last, scale, 1.0f / scale, pts,
                                                                                           index, n, n_device, sdf_out, nullptr, nullptr);
     return gens_launch_status("gens_sdf_value_bf16x3");
 }
@@ -539,9 +603,8 @@ extern "C" int gens_sdf_grad_bf16x3(const float* const* vols_packed, const int* 
                    "gens_sdf_grad_bf16x3: null or misaligned stash (gens_sdf_grad_f16_stash_bytes() bytes, zeroed once)");
     GENS_CHECK_ARG(gens_sdf_grad_f16_stash_bytes() == (int64_t)GB_SLOTS * GB_SLOT_BYTES, GENS_EINVAL, "gens_sdf_grad_bf16x3: stash layout differs from k6gh's");
     if (n == 0) return 0;
-    static GensLdsOptIn lds3, lds5;
-    if (int e = n_levels == 3 ? gens_lds_opt_in(lds3, (const void*)sdf_bf16x3_k<3, true>, GB_LDS_BYTES, "gens_sdf_grad_bf16x3")
-                              : gens_lds_opt_in(lds5, (const void*)sdf_bf16x3_k<5, true>, GB_LDS_BYTES, "gens_sdf_grad_bf16x3"))
+    if (int e = n_levels == 3 ? gens_lds_opt_in(g_grad_lds3, (const void*)sdf_bf16x3_k<3, true>, GB_LDS_BYTES, "gens_sdf_grad_bf16x3")
+                              : gens_lds_opt_in(g_grad_lds5, (const void*)sdf_bf16x3_k<5, true>, GB_LDS_BYTES, "gens_sdf_grad_bf16x3"))
         return e;
     const unsigned grid = gens_blocks(n, 32 * GB_WAVES);
     if (n_levels == 3)
@@ -551,4 +614,30 @@ extern "C" int gens_sdf_grad_bf16x3(const float* const* vols_packed, const int* 
         sdf_bf16x3_k<5, true><<<grid, 64 * GB_WAVES, GB_LDS_BYTES, (hipStream_t)stream>>>(vs, (const char*)pieces, w_out, b_last, scale, 1.0f / scale, pts,
                                                                                            index, n, n_device, sdf_out, grad_out, (char*)stash);
     return gens_launch_status("gens_sdf_grad_bf16x3");
+}
+
+// What the device says about one instantiation at the launcher's own block and LDS sizes: registers per lane, scratch bytes per lane, dynamic
+// LDS bytes, resident workgroups per CU.
+extern "C" int gens_sdf_bf16x3_residency(int n_levels, int grad, int out[4]) {
+    GENS_CHECK_ARG(n_levels == 3 || n_levels == 5, GENS_ELIMIT, "gens_sdf_bf16x3_residency: built for 3 or 5 volume levels, got %d", n_levels);
+    GENS_CHECK_ARG(out, GENS_EINVAL, "gens_sdf_bf16x3_residency: null output");
+    const void* fn = grad ? (n_levels == 3 ? (const void*)sdf_bf16x3_k<3, true> : (const void*)sdf_bf16x3_k<5, true>)
+                          : (n_levels == 3 ? (const void*)sdf_bf16x3_k<3, false> : (const void*)sdf_bf16x3_k<5, false>);
+    const int lds = grad ? GB_LDS_BYTES : n_levels == 3 ? GB_VALUE_LDS_BYTES(3) : GB_VALUE_LDS_BYTES(5);
+    if (grad)
+        if (int e = gens_lds_opt_in(n_levels == 3 ? g_grad_lds3 : g_grad_lds5, fn, GB_LDS_BYTES, "gens_sdf_bf16x3_residency")) return e;
+    hipFuncAttributes attr;
+    int blocks = 0;
+    hipError_t err = hipFuncGetAttributes(&attr, fn);
+    if (err == hipSuccess) err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, 64 * GB_WAVES, lds);
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        gens_set_error("gens_sdf_bf16x3_residency: %s", hipGetErrorString(err));
+        return (int)err;
+    }
+    out[0] = attr.numRegs;
+    out[1] = (int)attr.localSizeBytes;
+    out[2] = lds;
+    out[3] = blocks;
+    return 0;
 }

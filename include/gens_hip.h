@@ -55,7 +55,8 @@ const char* gens_last_error(void);
  *   12 = round 6: gens_upsample2d_cat (the warp features in one launch), gens_volume_build_levels_bits (the volume build leaves the masks as bits
  *       too), gens_select_views (the views of a fine-tune step out of the frozen maps and their layouts in one launch),
  *       gens_lookup_volume_bwd_bricks / _bwd2_bricks + gens_lookup_scatter_bricks_scratch_bytes (K2's volume-gradient scatter brick by brick).
- *       Later additions that change no existing entry keep 12: gens_sdf_{value,grad}_bf16x3 + gens_sdf_bf16x3_pieces, and K23's
+ *       Later additions that change no existing entry keep 12: gens_sdf_{value,grad}_bf16x3 + gens_sdf_bf16x3_pieces (+ gens_sdf_bf16x3_residency),
+ *       and K23's
  *       gens_mesh_grid_{count,fill}, gens_ray_first_hit, gens_view_rays_hit_faces, gens_face_cc_{hook,compress}, and K24's
  *       gens_mesh_sample_{count,emit}, gens_point_grid_{count,fill}, gens_radius_downsample_round, gens_nearest_point, and K25's
  *       gens_dilate_u8, gens_vertex_mask_votes, gens_view_rays_hit_counts, and K26's gens_filter_masks, gens_filter_band, gens_filter_levels,
@@ -396,6 +397,10 @@ int gens_sdf_grad_bf16x3(const float* const* vols_packed, const int* dims, int n
                          float* sdf_out, float* grad_out, void* stash, void* stream);
 /* number of 1 KB pieces in the weight stream of gens_sdf_value_bf16x3 / gens_sdf_grad_bf16x3, padding included (0 = unsupported level count) */
 int gens_sdf_bf16x3_pieces(int n_levels);
+/* residency of one instantiation (grad: 0 = gens_sdf_value_bf16x3's kernel, 1 = gens_sdf_grad_bf16x3's) on the current device, at the launcher's
+ * block and LDS sizes: out[0] registers per lane (hipFuncAttributes.numRegs), out[1] scratch bytes per lane (localSizeBytes), out[2] dynamic LDS
+ * bytes of a launch, out[3] resident workgroups per CU (hipOccupancyMaxActiveBlocksPerMultiprocessor).  out: HOST, 4 ints. */
+int gens_sdf_bf16x3_residency(int n_levels, int grad, int out[4]);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K21  depth-wise 2-D convolutions of the MnasNet trunk (k21_depthwise.hip): nn.Conv2d(c, c, k, padding = k / 2, stride, groups = c,
