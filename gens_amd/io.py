@@ -73,6 +73,12 @@ def write_ply(path, vertices, triangles, normals=None, colors=None):
         f.write(faces.tobytes())
 
 
+def write_point_cloud(path, points, normals=None, colors=None):
+    """A point cloud as write_ply writes a mesh, with an empty face element (read_ply reads it back: triangles of shape (0, 3)): float32
+    x y z, optional float nx ny nz and uchar red green blue.  What evaluate_dtu(mode="pcd") reads as pcd/scan{n}.ply."""
+    write_ply(path, points, np.zeros((0, 3), np.int32), normals=normals, colors=colors)
+
+
 _PLY_TYPES = {b"char": "i1", b"int8": "i1", b"uchar": "u1", b"uint8": "u1", b"short": "<i2", b"int16": "<i2", b"ushort": "<u2", b"uint16": "<u2",
               b"int": "<i4", b"int32": "<i4", b"uint": "<u4", b"uint32": "<u4", b"float": "<f4", b"float32": "<f4", b"double": "<f8",
               b"float64": "<f8"}
@@ -282,7 +288,10 @@ def save_validation_outputs(base_exp_dir, outputs, inputs, tag, image_tag=None, 
     output is arbitrary there) are written mid-grey (128, 128, 128).
     outputs["surface_depth"] / ["surface_normal_img"] / ["surface_img"] (validate's surface_render), where present, are written under
     val_surface_depth/, val_surface_normal/ and val_surface_img/ by the writers of their volume-rendered counterparts; pixels whose ray did
-    not hit the surface are black."""
+    not hit the surface are black.
+    outputs["fused_points"] (validate's surface_fusion), where present, is written as pcd/{scene}_{tag}.ply (write_point_cloud) in world
+    coordinates (transform_vertices / transform_normals with scale_mat), with fused_normals and fused_colors where present; colours of points
+    no source view sees (fused_seen False) are written mid-grey.  Copied to pcd/scan{n}.ply it is what evaluate_dtu(mode="pcd") reads."""
     if clean_frustum and not clean:
         raise ValueError("save_validation_outputs: clean_frustum=True needs clean=True")
     scene = inputs["scene"]
@@ -323,4 +332,12 @@ def save_validation_outputs(base_exp_dir, outputs, inputs, tag, image_tag=None, 
         if outputs.get("surface_hit") is not None:        # (the colour map's lowest entry is not quite black)
             rgb = np.where(np.asarray(outputs["surface_hit"], dtype=bool)[:, :, None], rgb, np.uint8(0))
         Image.fromarray(rgb).save(paths[name])
+    if "fused_points" in outputs:
+        os.makedirs(os.path.join(base_exp_dir, "pcd"), exist_ok=True)
+        paths["pcd"] = os.path.join(base_exp_dir, "pcd", f"{scene}_{tag}.ply")
+        cloud_normals, cloud_colors = outputs.get("fused_normals"), outputs.get("fused_colors")
+        if cloud_colors is not None and outputs.get("fused_seen") is not None:
+            cloud_colors = np.where(np.asarray(outputs["fused_seen"], dtype=bool)[:, None], cloud_colors, np.uint8(128))
+        write_point_cloud(paths["pcd"], transform_vertices(outputs["fused_points"], scale_mat),
+                          normals=None if cloud_normals is None else transform_normals(cloud_normals, scale_mat), colors=cloud_colors)
     return paths

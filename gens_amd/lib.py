@@ -225,6 +225,8 @@ SIGNATURES = {
     "gens_trace_refine": [C.POINTER(TraceState), _p, _p, _l, _f, _i, _p],
     "gens_trace_gather": [_p, _p, _l, _l, _p, _p],
     "gens_surface_pack": [C.POINTER(SurfacePackArgs), _p],
+    "gens_fuse_depth_maps": [_p, _p, _p, _p, _i, _i, _i, _i, _d, _d, _i, _d, _p, _p, _p, _p],
+    "gens_fused_points": [_p, _p, _p, _l, _i, _i, _i, _p, _p, _p, _p, _p, _p],
 }
 
 _lib = None

@@ -103,6 +103,9 @@ class GenS(nn.Module):
         surface = confs.get("surface_render", None)             # optional: validate also traces its rays to the surface (render_surface, K31); True or its keywords
         if surface is not None:
             self.implicit_surface.surface_render = dict(surface) if hasattr(surface, "keys") else bool(surface)
+        fusion = confs.get("surface_fusion", None)              # optional: validate also fuses the views' traced depth maps into a point cloud (fuse_surface, K32); True or its keywords
+        if fusion is not None:
+            self.implicit_surface.surface_fusion = dict(fusion) if hasattr(fusion, "keys") else bool(fusion)
         lipschitz = confs.get("lattice_lipschitz", None)        # optional: the bound that lattice assumes (ImplicitSurface.lattice_lipschitz)
         if lipschitz is not None:
             self.implicit_surface.lattice_lipschitz = float(lipschitz)

@@ -835,10 +835,19 @@ class ImplicitSurface(nn.Module):
         INSIDE and EXHAUSTED rays are counted in self.last_surface_stats (ops.sphere_trace's stats), not hidden.  The evaluator is the
         lattice's (_lattice_passes): this scene's sdf_precision, and a split-half overflow repeats the whole trace in float32; no mask
         volume is consulted.  ValueError before any launch for what _attribute_request refuses and for a bad lipschitz / min_step / max_steps."""
+        shape = tuple(int(v) for v in hw) if hw is not None else tuple(rays_o.shape[:-1])
+        out = self._trace_surface(rays_o, rays_d, near, far, volumes, bound_min, bound_max, c2ws, views, outputs, resolution, threshold, chunk,
+                                  lipschitz, min_step, max_steps, refine)
+        return {k: v.cpu().numpy().reshape(shape + tuple(v.shape[1:])) for k, v in out.items()}
+
+    @torch.no_grad()
+    def _trace_surface(self, rays_o, rays_d, near, far, volumes, bound_min, bound_max, c2ws, views, outputs, resolution, threshold, chunk, lipschitz,
+                       min_step, max_steps, refine):
+        """render_surface on the device: its arguments -> its dict as flat per-ray device tensors (nothing is copied to the host but the
+        counts the trace reads anyway); self.last_surface_stats as render_surface leaves it."""
         names, lipschitz, min_step, max_steps, refine = self._surface_request(outputs, volumes, views, resolution, lipschitz, min_step, max_steps,
                                                                               refine, bound_min, bound_max)
         vols = volumes if isinstance(volumes, ops.VolumeSet) else ops.VolumeSet.packed(volumes)
-        shape = tuple(int(v) for v in hw) if hw is not None else tuple(rays_o.shape[:-1])
         o, d = rays_o.reshape(-1, 3), rays_d.reshape(-1, 3)
         lo, hi = bound_min.tolist(), bound_max.tolist()
         traced, stats = self._lattice_passes(vols, None, lambda evaluate: ops.trace_rays(
@@ -863,7 +872,107 @@ class ImplicitSurface(nn.Module):
             out["seen"] = packed.get("seen", torch.zeros(n, device=o.device, dtype=torch.uint8)).bool()
         if "depth" not in names:
             del out["depth"]
-        return {k: v.cpu().numpy().reshape(shape + tuple(v.shape[1:])) for k, v in out.items()}
+        return out
+
+    surface_fusion = None          # validate also fuses the sphere-traced depth maps of the item's views into a point cloud (fuse_surface, K32) and
+                                   # returns fused_points, fused_normals, fused_colors and fused_seen.  None / False: off; True: on; or a dict of
+                                   # fuse_surface's keywords (pairs, pix_tol, rel_tol, min_views, normal_cos, dedupe_radius, and render_surface's)
+                                   # 
+    last_fusion_stats = None       # per view: usable and kept pixels, the votes histogram and the trace stats of the last fuse_surface call
+    _FUSION_KEYS = ("pix_tol", "rel_tol", "min_views", "normal_cos")
+    _FUSION_TRACE_KEYS = ("resolution", "threshold", "chunk", "lipschitz", "min_step", "max_steps", "refine")
+
+    @staticmethod
+    def view_rays(intrs, c2ws, v, hw):
+        """The rays of every pixel of view v, formed on the device of intrs / c2ws with synthetic.make_rays' arithmetic (dtu.py:390-403):
+        pixel (x, y), integers, is the ray through K^-1 [x, y, 1], normalised and rotated by the pose -> (rays_o, rays_d) (H W, 3) float32."""
+        h, w = int(hw[0]), int(hw[1])
+        dev = c2ws.device
+        py, px = torch.meshgrid(torch.linspace(0, h - 1, h, device=dev), torch.linspace(0, w - 1, w, device=dev), indexing="ij")
+        px, py = px.reshape(-1), py.reshape(-1)
+        p = torch.stack([px, py, torch.ones_like(py)], dim=-1)
+        p = (torch.inverse(intrs[v, :3, :3].float())[None] @ p[:, :, None])[:, :, 0]
+        d = p / torch.linalg.norm(p, dim=-1, keepdim=True)
+        rays_d = (c2ws[v, :3, :3].float()[None] @ d[:, :, None])[:, :, 0]
+        rays_o = c2ws[v, :3, 3].float()[None].expand_as(rays_d).contiguous()
+        return rays_o, rays_d.contiguous()
+
+    @torch.no_grad()
+    def fuse_surface(self, volumes, intrs, c2ws, hw, bound_min, bound_max, views=None, pairs=None, near=None, far=None,
+                     attributes=("normals", "colors"), dedupe_radius=None, **keywords):
+        """The surface as a fused point cloud (K32): every view of the scene is traced to the surface (render_surface's
+        machinery with that view's pose, so the depth is the view's own z-depth), the maps stay on the device, and a pixel is kept when at
+        least min_views of the views `pairs` lists for it confirm its surface point (ops.fuse_depth_maps); the kept pixels are averaged with
+        their voters and lifted (ops.fused_points).  intrs, c2ws (nv, 4, 4) device tensors, hw = (H, W); views: the scene's ops.SceneViews,
+        needed for "colors"; near (default 0) / far (default: the largest distance from a camera centre to a corner of the box, so that the
+        slab test alone bounds a ray): one value each.  keywords: ops.fuse_depth_maps' pix_tol, rel_tol, min_views, normal_cos (needs
+        "normals") and render_surface's resolution, threshold, chunk, lipschitz, min_step, max_steps, refine.
+        -> dict of host arrays: "points" (N, 3) float64, "view" (N,) int32 and "pixel" (N,) int64 (the flat index (view H + y) W + x), and
+        "normals" (N, 3) float32 / "colors" (N, 3) uint8 with "seen" (N,) bool as `attributes` names them.  A surface point is emitted by
+        every view that keeps it unless dedupe_radius thins the cloud (ops.fused_points).  Where "seen" is False no source view has the
+        point in its frustum and the colour is arbitrary: the point stays, writers colour it mid-grey.  self.last_fusion_stats: per view
+        "usable", "kept", "votes" (histogram, index = votes) and "trace" (ops.sphere_trace's stats), and "points".
+        ValueError before any launch for what _attribute_request, _surface_request and ops.fuse_depth_maps refuse."""
+        unknown = [k for k in keywords if k not in self._FUSION_KEYS + self._FUSION_TRACE_KEYS]
+        if unknown:
+            raise TypeError(f"fuse_surface: unknown keywords {unknown!r}")
+        fusion_kw = {k: keywords[k] for k in self._FUSION_KEYS if k in keywords}
+        trace_kw = {"resolution": 512, "threshold": 0.0, "chunk": 1 << 21, "lipschitz": None, "min_step": None, "max_steps": 256, "refine": 2,
+                    **{k: keywords[k] for k in self._FUSION_TRACE_KEYS if k in keywords}}
+        names = self._attribute_request(attributes, volumes, views) if attributes is not None else ()
+        outputs = ("depth",) + names
+        self._surface_request(outputs, volumes, views, trace_kw["resolution"], trace_kw["lipschitz"], trace_kw["min_step"], trace_kw["max_steps"],
+                              trace_kw["refine"], bound_min, bound_max)
+        h, w = int(hw[0]), int(hw[1])
+        if h < 1 or w < 1:
+            raise ValueError(f"fuse_surface: hw = {tuple(hw)!r}")
+        cams = ops.fusion_cams(intrs, c2ws)
+        nv = cams.shape[0]
+        want_n, want_c = "normals" in names, "colors" in names
+        pairs, pix_tol, rel_tol, min_views, normal_cos = ops.fusion_request(
+            "fuse_surface", nv, pairs, fusion_kw.get("pix_tol", 1.0), fusion_kw.get("rel_tol", 0.01), fusion_kw.get("min_views", 3), want_n,
+            fusion_kw.get("normal_cos"))
+        dedupe_radius = ops._radius("fuse_surface", dedupe_radius)
+        if nv * h * w >= 2 ** 31:
+            raise ValueError(f"fuse_surface: {nv} maps of {h} x {w} pixels (nv H W below 2^31)")
+        dev = c2ws.device
+        lo, hi = bound_min.detach().double().cpu(), bound_max.detach().double().cpu()
+        near = torch.full((1,), 0.0 if near is None else float(near), device=dev)
+        if far is None:
+            corners = torch.stack([torch.stack([(lo, hi)[(i >> a) & 1][a] for a in range(3)]) for i in range(8)])
+            far = float((corners[None] - torch.as_tensor(cams[:, 21:])[:, None]).norm(dim=-1).max())
+        far = torch.full((1,), float(far), device=dev)
+        depth = torch.empty(nv, h, w, device=dev)
+        normal = torch.empty(nv, h, w, 3, device=dev) if want_n else None
+        img = torch.empty(nv, h, w, 3, device=dev, dtype=torch.uint8) if want_c else None
+        seen = torch.empty(nv, h, w, device=dev, dtype=torch.bool) if want_c else None
+        trace_stats = []
+        for v in range(nv):
+            o, d = self.view_rays(intrs, c2ws, v, (h, w))
+            maps = self._trace_surface(o, d, near, far, volumes, bound_min, bound_max, c2ws[[v]], views, outputs, trace_kw["resolution"],
+                                       trace_kw["threshold"], trace_kw["chunk"], trace_kw["lipschitz"], trace_kw["min_step"],
+                                       trace_kw["max_steps"], trace_kw["refine"])
+            trace_stats.append(self.last_surface_stats)
+            depth[v] = maps["depth"].view(h, w)
+            if want_n:
+                normal[v] = maps["normal"].view(h, w, 3)
+            if want_c:
+                img[v], seen[v] = maps["img"].view(h, w, 3), maps["seen"].view(h, w)
+        votes, keep, fused = ops.fuse_depth_maps(depth, cams, pairs, pix_tol, rel_tol, min_views, normal if normal_cos is not None else None,
+                                                 normal_cos)
+        points, normals, colors, pixel = ops.fused_points(fused, cams, keep, normal, img, dedupe_radius)
+        usable = (torch.isfinite(depth) & (depth > 0)).view(nv, -1).sum(dim=1).tolist()
+        kept = keep.view(nv, -1).sum(dim=1).tolist()
+        hist = [torch.bincount(votes[v].reshape(-1).long(), minlength=pairs.shape[1] + 1).tolist() for v in range(nv)]
+        self.last_fusion_stats = {"points": int(points.shape[0]), "views": [
+            {"usable": int(usable[v]), "kept": int(kept[v]), "votes": hist[v], "trace": trace_stats[v]} for v in range(nv)]}
+        out = {"points": points.cpu().numpy(), "view": (pixel // (h * w)).to(torch.int32).cpu().numpy(), "pixel": pixel.cpu().numpy()}
+        if want_n:
+            out["normals"] = normals.cpu().numpy()
+        if want_c:
+            out["colors"] = colors.cpu().numpy()
+            out["seen"] = seen.view(-1)[pixel].cpu().numpy()
+        return out
 
     def extract_geometry(self, volumes, bound_min, bound_max, resolution, threshold, shard=None, sparse=None, sparse_mesh=None, attributes=None,
                          views=None):
@@ -905,7 +1014,7 @@ class ImplicitSurface(nn.Module):
     @torch.no_grad()
     def validate(self, rays_o, rays_d, near, far, volumes, mask_volumes, imgs, features, match_features, intrs, c2ws, bound_min, bound_max,
                  hw, cos_anneal_ratio=1.0, step=None, extract_geometry=True, mesh_resolution=512, threshold=0.0, scene=None, shard=None, sparse=None,
-                 sparse_mesh=None, mesh_attributes=None, surface_render=None):
+                 sparse_mesh=None, mesh_attributes=None, surface_render=None, surface_fusion=None):
         """shard (gens_amd.distributed.Shard, optional): render only this rank's contiguous ray range and evaluate only its lattice
         chunks; the (P, 8) image buffer / the lattice slabs are gathered over RCCL, so every rank returns the whole image.  The jitter
         of EVERY ray is drawn on every rank from the identically seeded CPU generator (the reference's draw order) and sliced with
@@ -913,8 +1022,17 @@ class ImplicitSurface(nn.Module):
         on its bricks).  mesh_attributes: extract_geometry's `attributes` with this scene's views -> outputs["vertex_normals"],
         ["vertex_colors"], ["vertex_seen"] beside the mesh.  surface_render (default: the attribute of that name, None / False = off; True, or
         a dict of render_surface's keywords): the rays of this image are also traced to the surface (render_surface, K31) ->
-        outputs["surface_depth"], ["surface_normal_img"], ["surface_img"], ["surface_hit"]; not with a shard."""
+        outputs["surface_depth"], ["surface_normal_img"], ["surface_img"], ["surface_hit"]; not with a shard.  surface_fusion (default: the
+        attribute of that name, None / False = off; True, or a dict of fuse_surface's keywords): every view of this item (its intrs, c2ws, hw
+        and views) is traced to the surface and the depth maps are fused into a point cloud (fuse_surface, K32) -> outputs["fused_points"],
+        ["fused_normals"], ["fused_colors"], ["fused_seen"]; not with a shard."""
         outputs = {}
+        surface_fusion = self.surface_fusion if surface_fusion is None else surface_fusion
+        if surface_fusion:
+            if shard is not None:
+                raise ValueError("surface_fusion is not sharded: fuse the views on one rank (fuse_surface)")
+            fusion_kw = {"resolution": mesh_resolution, **(surface_fusion if isinstance(surface_fusion, dict) else {})}
+            fusion_kw["attributes"] = ("normals", "colors")
         surface_render = self.surface_render if surface_render is None else surface_render
         if surface_render:
             if shard is not None:
@@ -1012,6 +1130,11 @@ class ImplicitSurface(nn.Module):
                                        threshold=threshold, hw=(height, width), **surface_kw)
             outputs["surface_depth"], outputs["surface_normal_img"] = surf["depth"], surf["normal_img"]
             outputs["surface_img"], outputs["surface_hit"] = surf["img"], surf["hit"]
+        if surface_fusion:
+            cloud = self.fuse_surface(scene.volumes_nograd(), intrs, c2ws, (height, width), bound_min, bound_max, views=scene.views,
+                                      **{"threshold": threshold, **fusion_kw})
+            outputs["fused_points"], outputs["fused_normals"] = cloud["points"], cloud["normals"]
+            outputs["fused_colors"], outputs["fused_seen"] = cloud["colors"], cloud["seen"]
         return outputs
 
     def val_chunk_for(self, n_rays):

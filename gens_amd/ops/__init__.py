@@ -26,6 +26,7 @@ is what it was when ops was one module:
     ops.brick_mcubes  K29: marching cubes on that lattice's bricks, without the dense lattice (brick_marching_cubes).
     ops.vertex_attrs  K30: per-vertex attributes of an extracted mesh: lattice vertices to points, gradient / colour to normals / 8-bit colours.
     ops.trace     K31: sphere tracing of the surface along rays (sphere_trace) and the per-ray depth / normal / colour pack (surface_pack).
+    ops.fusion    K32: per-view depth maps fused into a consistency-filtered point cloud (fusion_cams, fuse_depth_maps, fused_points).
 """
 from .base import *  # noqa: F401,F403
 from .volume import *  # noqa: F401,F403
@@ -44,3 +45,4 @@ from .lattice import *  # noqa: F401,F403
 from .brick_mcubes import *  # noqa: F401,F403
 from .vertex_attrs import *  # noqa: F401,F403
 from .trace import *  # noqa: F401,F403
+from .fusion import *  # noqa: F401,F403

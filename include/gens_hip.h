@@ -64,7 +64,7 @@ const char* gens_last_error(void);
  *       gens_sparse_classify, gens_sparse_brick_points, gens_sparse_fill, gens_sparse_scatter, gens_sparse_leaks, and K29's
  *       gens_brick_coarse_points, gens_brick_points, gens_brick_active, gens_brick_emit_flags, gens_brick_mc_classify, gens_brick_mc_emit,
  *       and K30's gens_vertex_points, gens_vertex_pack, and K31's gens_trace_begin, gens_trace_march, gens_trace_refine, gens_trace_gather,
- *       gens_surface_pack. */
+ *       gens_surface_pack, and K32's gens_fuse_depth_maps, gens_fused_points. */
 int gens_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -1010,6 +1010,44 @@ int gens_trace_march(const gens_trace_state* s, const float* sdf, const int64_t*
 int gens_trace_refine(const gens_trace_state* s, const float* sdf, const int64_t* idx, int64_t m, float threshold, int final, void* stream);
 int gens_trace_gather(const float* points, const int64_t* idx, int64_t m, int64_t n, float* out, void* stream);
 int gens_surface_pack(const gens_surface_pack_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * K32  Fusion of per-view depth maps into a consistency-filtered point cloud (ops.fuse_depth_maps, ops.fused_points,
+ *      ImplicitSurface.fuse_surface), csrc/k32_depth_fusion.hip.  tests/depth_fusion_reference.py restates all of it in numpy.
+ *
+ *   Definition.  All arithmetic is float64, every operation rounded on its own, in the order written; no square root: distances are
+ *   compared squared.  A NaN makes a comparison false, hence no vote; nothing special-cases it.
+ *     depth (nv, H, W) float32: each view's z-depth in its own camera; a pixel is usable iff its depth is finite and > 0.
+ *     cams (nv, 24) float64 per view: P = K[:3,:3] w2c[:3,:4] (12, row-major), B = inverse(K[:3,:3] w2c[:3,:3]) (9, row-major), the camera
+ *       centre c (3).  Pixel (x, y), integers, is the ray through K^-1 [x, y, 1].  Below
+ *         B [x, y, 1] = (B[i][0] x + B[i][1] y) + B[i][2]                    per row i
+ *         P [X, 1]    = ((P[i][0] X0 + P[i][1] X1) + P[i][2] X2) + P[i][3]   per row i.
+ *     pairs (nv, k) int32: row r lists the source views that vote for view r; an entry outside 0 .. nv - 1 is skipped (-1 pads a row).
+ *     For a usable pixel (r, y, x) with depth d:  X = c_r + d (B_r [x, y, 1]);  n = 0, dsum = 0;  for each listed source s, in list order:
+ *       q = P_s [X, 1]; no vote unless q_z > 0.  xs = q_x / q_z, ys = q_y / q_z, x0 = floor(xs), y0 = floor(ys).
+ *       No vote unless 0 <= x0, x0 + 1 <= W - 1, 0 <= y0, y0 + 1 <= H - 1, and unless the taps d00 = depth[s, y0, x0], d01 = [s, y0, x0 + 1],
+ *       d10 = [s, y0 + 1, x0], d11 = [s, y0 + 1, x0 + 1] are all usable.  fx = xs - x0, fy = ys - y0,
+ *       ds = (d00 (1 - fx) + d01 fx) (1 - fy) + (d10 (1 - fx) + d11 fx) fy,   Xs = c_s + ds (B_s [xs, ys, 1]),
+ *       q' = P_r [Xs, 1]; no vote unless q'_z > 0.  ex = q'_x / q'_z - x, ey = q'_y / q'_z - y.
+ *       Vote iff ex ex + ey ey < pix_tol pix_tol and |q'_z - d| / d < rel_tol (both strict), and, with a normal map (nv, H, W, 3) float32,
+ *       (n_a0 n_b0 + n_a1 n_b1) + n_a2 n_b2 >= normal_cos for n_a = normal[r, y, x], n_b = normal[s, floor(ys + 0.5), floor(xs + 0.5)].
+ *       On a vote n += 1, dsum += q'_z.
+ *     votes[r, y, x] = min(n, 255); keep = (n >= min_views); fused = (d + dsum) / (n + 1) where kept, else 0 (float64); an unusable pixel
+ *     has 0 votes.  point = c_r + fused (B_r [x, y, 1]).
+ *   gens_fuse_depth_maps: one thread per reference pixel, a workgroup on 16 x 16 pixels of one view (8 x 8 per wave) -> votes, keep (nv, H, W)
+ *     uint8, fused (nv, H, W) float64.  normal == NULL: no normal test.  All pointers are device pointers.
+ *   gens_fused_points: list (n_list) int64 flat pixel indices (r H + y) W + x (gens_compact_valid of keep) -> points (n_list, 3) float64, and
+ *     normals (n_list, 3) float32 / colors (n_list, 3) uint8 copied from normal (nv, H, W, 3) / img (nv, H, W, 3) uint8 at the pixel (a map
+ *     and its output are given together or both NULL).  An entry outside the maps gives zero rows.
+ *   Arguments are checked before any launch: negative sizes, k < 0, pix_tol / rel_tol negative or not finite, min_views < 1, a NaN
+ *   normal_cos with a normal map, null pointers: GENS_EINVAL; nv H W or n_list >= 2^31: GENS_ELIMIT.  nv H W == 0 / n_list == 0 succeed
+ *   without a launch.  The ABI version stays 12: no existing entry changes.
+ * ---------------------------------------------------------------------------------------------------------- */
+int gens_fuse_depth_maps(const float* depth, const double* cams, const int32_t* pairs, const float* normal, int nv, int h, int w, int k,
+                         double pix_tol, double rel_tol, int min_views, double normal_cos, uint8_t* votes, uint8_t* keep, double* fused,
+                         void* stream);
+int gens_fused_points(const double* fused, const double* cams, const int64_t* list, int64_t n_list, int nv, int h, int w, const float* normal,
+                      const uint8_t* img, double* points, float* normals, uint8_t* colors, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K14  C (m x n) = A^T B for tall row-major operands A (k x m), B (k x n), k >> m, n: the weight-gradient product of the training
