@@ -253,6 +253,36 @@ def clean_mesh(vertices, triangles, masks, intrs, c2ws, dilation_radius=11, min_
     return clean_mesh_outside_frustum(v_np, kept, masks, intrs, c2ws, upscale=upscale, min_faces=min_faces, return_index=return_index)
 
 
+@torch.no_grad()
+def simplify_mesh(vertices, triangles, cell, origin=None, normals=None, colors=None, seen=None, device=None, reg=1e-3):
+    """ops.simplify_mesh (K33: vertex clustering with quadric-optimal representatives) for host meshes, numpy in and out like the cleaners:
+    vertices (V,3), triangles (F,3) (arrays or tensors), cell: the edge of the clustering cells in the vertices' units; origin, reg:
+    ops.simplify_mesh's -> (vertices' (V',3) float64, triangles' (F',3) of the input's integer type, attrs).  attrs["source"] (V',) int64:
+    per returned vertex the input vertex nearest to it within its cluster; normals / colors / seen (V, ...), where given, come back in attrs
+    under those names gathered by it (attributes are never averaged: a colour stays a colour some vertex had).  attrs["stats"]:
+    ops.simplify_mesh's counts.  ValueError for what ops.simplify_mesh refuses, and for an attribute whose length is not V."""
+    from . import ops
+    v_np, t_np = as_numpy(vertices), as_numpy(triangles)
+    v_np = np.ascontiguousarray(v_np, dtype=np.float64).reshape(-1, 3)
+    given = {name: as_numpy(a) for name, a in (("normals", normals), ("colors", colors), ("seen", seen)) if a is not None}
+    for name, a in given.items():
+        if len(a) != len(v_np):
+            raise ValueError(f"simplify_mesh: {name} has {len(a)} rows for {len(v_np)} vertices")
+    t_int = np.asarray(t_np).reshape(-1, 3)
+    if t_int.size and (t_int.min() < 0 or t_int.max() >= len(v_np)):
+        raise ValueError(f"simplify_mesh: triangle indices {t_int.min()} .. {t_int.max()} outside the {len(v_np)} vertices")
+    if len(v_np) >= 2 ** 31:
+        raise ValueError(f"simplify_mesh: {len(v_np)} vertices (below 2^31)")
+    ops.simplify_request("simplify_mesh", cell, reg)
+    dev = device_of(vertices, triangles, device=device)
+    out_v, out_t, source, stats = ops.simplify_mesh(torch.from_numpy(v_np).to(dev), torch.from_numpy(np.ascontiguousarray(t_int, dtype=np.int32)).to(dev),
+                                                    cell, origin=origin, reg=reg)
+    source = source.cpu().numpy()
+    attrs = {name: a[source] for name, a in given.items()}
+    attrs["source"], attrs["stats"] = source, stats
+    return out_v.cpu().numpy(), out_t.cpu().numpy().astype(t_int.dtype if np.issubdtype(t_int.dtype, np.integer) else np.int32), attrs
+
+
 def dilate_masks(masks, radius=11):
     """utils/clean_mesh.py:119-125: masks (nv,H,W[,3]) > 0.5, dilated by a disk of `radius` pixels (skimage.morphology.disk)."""
     from scipy import ndimage

@@ -68,6 +68,12 @@ class SurfacePackArgs(C.Structure):   # gens_surface_pack_args (K31)
         (n, _p) for n in ("status", "t", "rays_d", "rot", "depth", "normal", "normal_img", "img", "seen", "hit")]
 
 
+class ClusterSolveArgs(C.Structure):  # gens_cluster_solve_args (K33)
+    _fields_ = [(n, _p) for n in ("vertices", "triangles", "survive", "cluster_keys", "entries", "entry_start", "members", "member_start", "out_clusters")] + [
+        (n, _l) for n in ("n_vertices", "n_triangles", "n_clusters", "n_out")] + [("origin", _d * 3), ("cell", _d), ("reg", _d)] + [
+        (n, _p) for n in ("out_vertices", "source", "fell_back")]
+
+
 # name -> argtypes, mirroring include/gens_hip.h declaration by declaration
 SIGNATURES = {
     "gens_pack_nchw": [_p, _p, _i, _i, _i, _i, _p],
@@ -227,6 +233,9 @@ SIGNATURES = {
     "gens_surface_pack": [C.POINTER(SurfacePackArgs), _p],
     "gens_fuse_depth_maps": [_p, _p, _p, _p, _i, _i, _i, _i, _d, _d, _i, _d, _p, _p, _p, _p],
     "gens_fused_points": [_p, _p, _p, _l, _i, _i, _i, _p, _p, _p, _p, _p, _p],
+    "gens_cluster_keys": [_p, _l, _d, _d, _d, _d, _p, _p],
+    "gens_cluster_triangles": [_p, _l, _p, _l, _p, _p, _p, _p],
+    "gens_cluster_solve": [C.POINTER(ClusterSolveArgs), _p],
 }
 
 _lib = None

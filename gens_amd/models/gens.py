@@ -106,6 +106,9 @@ class GenS(nn.Module):
         fusion = confs.get("surface_fusion", None)              # optional: validate also fuses the views' traced depth maps into a point cloud (fuse_surface, K32); True or its keywords
         if fusion is not None:
             self.implicit_surface.surface_fusion = dict(fusion) if hasattr(fusion, "keys") else bool(fusion)
+        simplify = confs.get("mesh_simplify", None)             # optional: extract_geometry / validate simplify the mesh on the device (ops.simplify_mesh, K33); a cell edge in lattice spacings
+        if simplify is not None:
+            self.implicit_surface.mesh_simplify = float(simplify)
         lipschitz = confs.get("lattice_lipschitz", None)        # optional: the bound that lattice assumes (ImplicitSurface.lattice_lipschitz)
         if lipschitz is not None:
             self.implicit_surface.lattice_lipschitz = float(lipschitz)

@@ -578,6 +578,19 @@ class ImplicitSurface(nn.Module):
     mesh_attributes = None         # ("normals", "colors") or one of them: extract_geometry / validate also return per-vertex attributes
                                    # (vertex_attributes, K30).  None / (): off
     VERTEX_ATTRIBUTES = ("normals", "colors")
+    mesh_simplify = None           # a cell edge in lattice spacings: extract_geometry / validate simplify the mesh on the device by quadric vertex
+                                   # clustering (ops.simplify_mesh, K33) before attributes and read-back.  None / False / 0: off
+    last_simplify_stats = None     # ops.simplify_mesh's stats of the last extract_geometry call (None: that call did not simplify)
+
+    def _simplify_request(self, simplify):
+        """The simplification a mesh call asks for (None: the attribute `mesh_simplify`) -> the cell edge in lattice spacings as a float, or
+        None for off (None, False, 0).  ValueError, before anything is launched, for anything else that is not a positive finite number."""
+        simplify = self.mesh_simplify if simplify is None else simplify
+        if simplify is None or simplify is False or (not isinstance(simplify, bool) and isinstance(simplify, (int, float)) and simplify == 0):
+            return None
+        if isinstance(simplify, bool):
+            raise ValueError("simplify = True: pass the cell edge in lattice spacings (a positive number; None, False or 0: off)")
+        return ops.simplify_request("simplify", simplify)[0]
 
     def _lattice_route(self, sparse, sparse_mesh, shard):
         """The options of sdf_grid (sparse_mesh=False) and extract_geometry -> (route, brick edge): "dense" (the dense lattice, brick None),
@@ -975,7 +988,7 @@ class ImplicitSurface(nn.Module):
         return out
 
     def extract_geometry(self, volumes, bound_min, bound_max, resolution, threshold, shard=None, sparse=None, sparse_mesh=None, attributes=None,
-                         views=None):
+                         views=None, simplify=None):
         """-> vertices (V,3) float64, triangles (T,3) int32 as numpy arrays (implicit_surface.py:407-427).  The SDF lattice and
         the marching cubes both run on the device (the reference: 512 D2H copies + PyMCubes on the host); only the mesh is copied.
         sparse: sdf_grid's option of that name, with this call's threshold.  sparse_mesh (default: the attribute of that name, None = off):
@@ -985,8 +998,17 @@ class ImplicitSurface(nn.Module):
         attributes (default: the attribute `mesh_attributes`, None / () = off): "normals", "colors" or both -> a third result, the dict of
         vertex_attributes at the float32 rounding of the returned vertices (formed on the device, gens_vertex_points, before the mesh is
         copied); views: the scene's ops.SceneViews, needed for the colours.  The same pass on every route, the leak fallback included; with a
-        shard, on every rank that holds the gathered mesh."""
+        shard, on every rank that holds the gathered mesh.
+        simplify (default: the attribute `mesh_simplify`; None, False or 0 = off): a cell edge in lattice spacings.  The device-resident mesh
+        is simplified by quadric vertex clustering (ops.simplify_mesh, K33) in index coordinates with origin (-0.5, -0.5, -0.5), so that for
+        whole-number edges lattice points are interior to cells -- after marching cubes on every route, the leak fallback included, before
+        the attribute pass (normals and colours are evaluated at the new vertices, not carried) and before the copy to the host; with a shard,
+        on every rank that holds the gathered mesh.  self.last_simplify_stats: its counts (None when off).  Topology is not preserved and no
+        distance to the surface is promised.  ValueError before any launch for a cell edge that is not a positive
+        finite number."""
         attributes = self._attribute_request(attributes, volumes, views)
+        simplify = self._simplify_request(simplify)
+        self.last_simplify_stats = None
         route, brick = self._lattice_route(sparse, sparse_mesh, shard)
         mesh = None
         if route == "mesh":
@@ -1002,6 +1024,8 @@ class ImplicitSurface(nn.Module):
                 return (None, None, None) if attributes else (None, None)
             mesh = ops.marching_cubes(u, threshold)
         vertices, triangles = mesh
+        if simplify is not None:
+            vertices, triangles, _, self.last_simplify_stats = ops.simplify_mesh(vertices, triangles, simplify, origin=(-0.5, -0.5, -0.5))
         b_max, b_min = bound_max.detach().cpu().numpy(), bound_min.detach().cpu().numpy()
         attrs = None
         if attributes:                                 # on the device-resident vertices; span: the host expression's (float32) difference, widened
@@ -1014,7 +1038,7 @@ class ImplicitSurface(nn.Module):
     @torch.no_grad()
     def validate(self, rays_o, rays_d, near, far, volumes, mask_volumes, imgs, features, match_features, intrs, c2ws, bound_min, bound_max,
                  hw, cos_anneal_ratio=1.0, step=None, extract_geometry=True, mesh_resolution=512, threshold=0.0, scene=None, shard=None, sparse=None,
-                 sparse_mesh=None, mesh_attributes=None, surface_render=None, surface_fusion=None):
+                 sparse_mesh=None, mesh_attributes=None, surface_render=None, surface_fusion=None, mesh_simplify=None):
         """shard (gens_amd.distributed.Shard, optional): render only this rank's contiguous ray range and evaluate only its lattice
         chunks; the (P, 8) image buffer / the lattice slabs are gathered over RCCL, so every rank returns the whole image.  The jitter
         of EVERY ray is drawn on every rank from the identically seeded CPU generator (the reference's draw order) and sliced with
@@ -1025,8 +1049,11 @@ class ImplicitSurface(nn.Module):
         outputs["surface_depth"], ["surface_normal_img"], ["surface_img"], ["surface_hit"]; not with a shard.  surface_fusion (default: the
         attribute of that name, None / False = off; True, or a dict of fuse_surface's keywords): every view of this item (its intrs, c2ws, hw
         and views) is traced to the surface and the depth maps are fused into a point cloud (fuse_surface, K32) -> outputs["fused_points"],
-        ["fused_normals"], ["fused_colors"], ["fused_seen"]; not with a shard."""
+        ["fused_normals"], ["fused_colors"], ["fused_seen"]; not with a shard.  mesh_simplify: extract_geometry's `simplify` (a cell edge in
+        lattice spacings; default: the attribute of that name, None / False / 0 = off): outputs["vertices"], ["triangles"] and the vertex
+        attributes are those of the simplified mesh (K33); self.last_simplify_stats holds its counts."""
         outputs = {}
+        mesh_simplify = self._simplify_request(mesh_simplify) if extract_geometry else None      # (refused before anything is launched)
         surface_fusion = self.surface_fusion if surface_fusion is None else surface_fusion
         if surface_fusion:
             if shard is not None:
@@ -1057,7 +1084,8 @@ class ImplicitSurface(nn.Module):
             import time
             t_geo = time.perf_counter()
             mesh = self.extract_geometry(scene.volumes_nograd(), bound_min, bound_max, mesh_resolution, threshold, shard=shard, sparse=sparse,
-                                         sparse_mesh=sparse_mesh, attributes=mesh_attributes, views=scene.views)
+                                         sparse_mesh=sparse_mesh, attributes=mesh_attributes, views=scene.views,
+                                         simplify=0 if mesh_simplify is None else mesh_simplify)
             outputs["vertices"], outputs["triangles"] = mesh[0], mesh[1]
             for name, values in ((mesh[2] or {}) if len(mesh) == 3 else {}).items():
                 outputs["vertex_" + name] = values

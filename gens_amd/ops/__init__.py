@@ -27,6 +27,7 @@ is what it was when ops was one module:
     ops.vertex_attrs  K30: per-vertex attributes of an extracted mesh: lattice vertices to points, gradient / colour to normals / 8-bit colours.
     ops.trace     K31: sphere tracing of the surface along rays (sphere_trace) and the per-ray depth / normal / colour pack (surface_pack).
     ops.fusion    K32: per-view depth maps fused into a consistency-filtered point cloud (fusion_cams, fuse_depth_maps, fused_points).
+    ops.simplify  K33: mesh simplification by vertex clustering with quadric-optimal representatives (simplify_mesh).
 """
 from .base import *  # noqa: F401,F403
 from .volume import *  # noqa: F401,F403
@@ -46,3 +47,4 @@ from .brick_mcubes import *  # noqa: F401,F403
 from .vertex_attrs import *  # noqa: F401,F403
 from .trace import *  # noqa: F401,F403
 from .fusion import *  # noqa: F401,F403
+from .simplify import *  # noqa: F401,F403

@@ -64,7 +64,8 @@ const char* gens_last_error(void);
  *       gens_sparse_classify, gens_sparse_brick_points, gens_sparse_fill, gens_sparse_scatter, gens_sparse_leaks, and K29's
  *       gens_brick_coarse_points, gens_brick_points, gens_brick_active, gens_brick_emit_flags, gens_brick_mc_classify, gens_brick_mc_emit,
  *       and K30's gens_vertex_points, gens_vertex_pack, and K31's gens_trace_begin, gens_trace_march, gens_trace_refine, gens_trace_gather,
- *       gens_surface_pack, and K32's gens_fuse_depth_maps, gens_fused_points. */
+ *       gens_surface_pack, and K32's gens_fuse_depth_maps, gens_fused_points, and K33's gens_cluster_keys, gens_cluster_triangles,
+ *       gens_cluster_solve. */
 int gens_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -1048,6 +1049,73 @@ int gens_fuse_depth_maps(const float* depth, const double* cams, const int32_t* 
                          void* stream);
 int gens_fused_points(const double* fused, const double* cams, const int64_t* list, int64_t n_list, int nv, int h, int w, const float* normal,
                       const uint8_t* img, double* points, float* normals, uint8_t* colors, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * K33  Mesh simplification by vertex clustering with quadric-optimal representatives (Lindstrom's out-of-core simplification;
+ *      ops.simplify_mesh, io.simplify_mesh, ImplicitSurface.extract_geometry(simplify=)), csrc/k33_mesh_simplify.hip.
+ *      tests/mesh_simplify_reference.py restates all of it in numpy.
+ *
+ *   Definition.  All arithmetic is float64, every operation rounded on its own, in the order written; no square root.
+ *     Inputs: vertices (V, 3) float64, triangles (T, 3) int32, cell > 0, origin (3), reg > 0 (default 1e-3).
+ *     1. Cell of a vertex p:  c_a = floor((p_a - origin_a) / cell) per axis, which needs 0 <= c_a < 2^21;  key = c_z 2^42 + c_y 2^21 + c_x
+ *        (int64).  The distinct keys in ascending order are the clusters (a cluster's rank is its place in that order); a cluster's members
+ *        are its vertices in ascending vertex index.
+ *     2. A triangle survives iff its three vertices lie in three different clusters.  Among surviving triangles with the same set of three
+ *        clusters, whatever the orientation, the one with the smallest triangle index is kept.  Kept triangles are emitted in ascending
+ *        input index with their own vertex order; output vertices are the clusters a kept triangle references, numbered in ascending key
+ *        order.
+ *     3. Quadric of a cluster, in cell units about the cluster's cell centre:  ctr_a = origin_a + (c_a + 0.5) cell,  q = (p - ctr) / cell.
+ *        For every SURVIVING triangle (before duplicate removal) that has a vertex in the cluster, in ascending triangle index, each once,
+ *        with its vertices q0, q1, q2 in stored order:  e1 = q1 - q0, e2 = q2 - q0,  n = e1 x e2 (n_x = e1_y e2_z - e1_z e2_y,
+ *        n_y = e1_z e2_x - e1_x e2_z, n_z = e1_x e2_y - e1_y e2_x: two rounded products and one subtraction each),
+ *        d = -((n_x q0_x + n_y q0_y) + n_z q0_z);  A_ij += n_i n_j for the six entries of the symmetric A,  b_i += n_i d.
+ *        m = (the sum of the members' q in member order) / their count.
+ *     4. Representative:  tr = (A00 + A11) + A22.  If not tr > 0, x = m.  Otherwise lambda = reg tr, M = A with lambda added on the
+ *        diagonal, r_a = lambda m_a - b_a, and M x = r is solved by the adjugate:
+ *          c00 = M11 M22 - M12 M12,  c01 = M02 M12 - M01 M22,  c02 = M01 M12 - M02 M11,
+ *          c11 = M00 M22 - M02 M02,  c12 = M01 M02 - M00 M12,  c22 = M00 M11 - M01 M01,
+ *          det = (M00 c00 + M01 c01) + M02 c02,
+ *          x_0 = ((c00 r0 + c01 r1) + c02 r2) / det,  x_1 = ((c01 r0 + c11 r1) + c12 r2) / det,  x_2 = ((c02 r0 + c12 r1) + c22 r2) / det.
+ *        If not det > 0, or any |x_a| <= 0.5 is false (a NaN included), x = m (the cluster "fell back", as it does when not tr > 0).
+ *        The output vertex is ctr_a + x_a cell.  The regulariser pulls towards the members' mean only along directions the planes do not
+ *        fix: a flat cluster gives the mean projected onto the plane, an edge cluster the mean projected onto the edge, a corner the corner.
+ *     5. Source vertex: the member with the smallest ((q_0 - x_0)^2 + (q_1 - x_1)^2) + (q_2 - x_2)^2, the first such member on ties.
+ *        Attributes are never averaged: callers gather any per-vertex array with it (normals[source]).
+ *   Guaranteed: every output vertex lies in its cluster's closed cell up to the rounding of the last multiply-add, hence within sqrt(3) cell
+ *   of its source vertex.  NOT guaranteed: topology (clustering can pinch sheets together, leave non-manifold edges and drop components
+ *   smaller than a cell), and any distance to the true surface.
+ *
+ *   gens_cluster_keys: one thread per vertex -> keys (V) int64; -1 where a c_a is outside 0 .. 2^21 - 1 or not a number (callers refuse
+ *     such input beforehand).
+ *   gens_cluster_triangles: one thread per triangle; vertex_cluster (V) int32 = each vertex's cluster rank -> ranks (T, 3) int32 (the three
+ *     ranks in stored order), survive (T) uint8, triple (T, 3) int32 (the ranks ascending).  A vertex index outside 0 .. V - 1 gives rank -1
+ *     and a triangle that does not survive.
+ *   gens_cluster_solve: one thread per output cluster j = 0 .. n_out - 1, cluster out_clusters[j].  cluster_keys (C) int64 ascending;
+ *     entries (3 T) int32: the values 3 t + k sorted stably by the rank of vertex k of triangle t, entry_start (C + 1) int32 the segment of
+ *     each cluster in it; members (V) int32: the vertex indices sorted stably by key, member_start (C + 1) int32.  The thread walks both
+ *     segments in order (steps 3 to 5) -> out_vertices (n_out, 3) float64, source (n_out) int32, fell_back (n_out) uint8.  Entries,
+ *     members and indices outside their ranges are skipped, never read through.
+ *   All pointers are device pointers.  Arguments are checked before any launch: negative sizes, cell / reg not positive and finite, an
+ *   origin that is not finite, n_clusters > n_vertices, n_out > n_clusters, null pointers: GENS_EINVAL; V or 3 T >= 2^31: GENS_ELIMIT.
+ *   V == 0, T == 0, n_out == 0 succeed without a launch.  The ABI version stays 12: no existing entry changes.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    const double* vertices;       /* (V, 3) */
+    const int32_t* triangles;     /* (T, 3) */
+    const uint8_t* survive;       /* (T) */
+    const int64_t* cluster_keys;  /* (C) */
+    const int32_t *entries, *entry_start, *members, *member_start, *out_clusters;
+    int64_t n_vertices, n_triangles, n_clusters, n_out;
+    double origin[3], cell, reg;
+    double* out_vertices;         /* (n_out, 3) */
+    int32_t* source;              /* (n_out) */
+    uint8_t* fell_back;           /* (n_out) */
+} gens_cluster_solve_args;
+int gens_cluster_keys(const double* vertices, int64_t n_vertices, double origin_x, double origin_y, double origin_z, double cell, int64_t* keys,
+                      void* stream);
+int gens_cluster_triangles(const int32_t* triangles, int64_t n_triangles, const int32_t* vertex_cluster, int64_t n_vertices, int32_t* ranks,
+                           uint8_t* survive, int32_t* triple, void* stream);
+int gens_cluster_solve(const gens_cluster_solve_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K14  C (m x n) = A^T B for tall row-major operands A (k x m), B (k x n), k >> m, n: the weight-gradient product of the training
