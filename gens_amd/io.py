@@ -79,6 +79,93 @@ def write_point_cloud(path, points, normals=None, colors=None):
     write_ply(path, points, np.zeros((0, 3), np.int32), normals=normals, colors=colors)
 
 
+def _obj_stem(path):
+    path = os.fspath(path)
+    return path[:-4] if path.lower().endswith(".obj") else path
+
+
+def write_obj(path, vertices, triangles, uv, texture, normals=None, seen=None):
+    """A textured mesh as Wavefront OBJ: `path`.obj (`path` may carry the extension), with its material `path`.mtl (map_Kd) and its texture
+    `path`.png beside it -- what MeshLab, Blender and Open3D open.  vertices (V,3) and optional per-vertex normals (V,3) are written as
+    float32 (`v`, `vn`), uv (T,3,2) (texture_mesh's "texture_uv": one coordinate pair per corner, origin bottom-left) as one `vt` per
+    corner, faces as `f a/ta[/na]`.  texture (H,W,3) uint8 (row 0 at the top); seen (H,W) bool, where given: texels no source view sees
+    (the network's output is arbitrary there) and texels no triangle owns are written mid-grey (128).  -> the three paths."""
+    stem = _obj_stem(path)
+    v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    t = np.ascontiguousarray(triangles, dtype=np.int64).reshape(-1, 3)
+    uv = np.ascontiguousarray(uv, dtype=np.float32).reshape(-1, 3, 2)
+    texture = np.asarray(texture)
+    if t.size and (t.min() < 0 or t.max() >= len(v)):
+        raise ValueError("write_obj: triangle index out of range")
+    if len(uv) != len(t):
+        raise ValueError(f"write_obj: {len(uv)} rows of corner coordinates for {len(t)} triangles")
+    if texture.ndim != 3 or texture.shape[2] != 3 or texture.dtype != np.uint8:
+        raise ValueError(f"write_obj: texture is {texture.shape} {texture.dtype}, expected (H, W, 3) uint8")
+    if normals is not None:
+        normals = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+        if len(normals) != len(v):
+            raise ValueError(f"write_obj: {len(normals)} normals for {len(v)} vertices")
+    if seen is not None:
+        seen = np.asarray(seen, dtype=bool)
+        if seen.shape != texture.shape[:2]:
+            raise ValueError(f"write_obj: seen is {seen.shape} for a texture of {texture.shape[:2]}")
+        texture = np.where(seen[:, :, None], texture, np.uint8(128))
+    name = os.path.basename(stem)
+    corner = 3 * np.arange(len(t), dtype=np.int64)[:, None] + np.arange(1, 4, dtype=np.int64)[None]
+    if normals is None:
+        faces, fmt = np.stack([t + 1, corner], axis=-1).reshape(-1, 6), "f %d/%d %d/%d %d/%d"
+    else:
+        faces, fmt = np.stack([t + 1, corner, t + 1], axis=-1).reshape(-1, 9), "f %d/%d/%d %d/%d/%d %d/%d/%d"
+    with open(stem + ".obj", "w") as f:
+        f.write(f"# gens_amd\nmtllib {name}.mtl\nusemtl {name}\n")
+        np.savetxt(f, v, fmt="v %.9g %.9g %.9g")
+        np.savetxt(f, uv.reshape(-1, 2), fmt="vt %.9g %.9g")
+        if normals is not None:
+            np.savetxt(f, normals, fmt="vn %.9g %.9g %.9g")
+        np.savetxt(f, faces, fmt=fmt)
+    with open(stem + ".mtl", "w") as f:
+        f.write(f"newmtl {name}\nKa 1 1 1\nKd 1 1 1\nKs 0 0 0\nillum 1\nmap_Kd {name}.png\n")
+    Image.fromarray(np.ascontiguousarray(texture)).save(stem + ".png")
+    return stem + ".obj", stem + ".mtl", stem + ".png"
+
+
+def read_obj(path):
+    """Inverse of write_obj -> dict: "vertices" (V,3) float32, "triangles" (T,3) int32, "uv" (T,3,2) float32, "normals" (V,3) float32 or
+    None, "texture" (H,W,3) uint8 (through the material's map_Kd; None if the file names none).  Reads what write_obj writes: triangles
+    whose corners are a/ta or a/ta/na, with the normal index equal to the vertex index."""
+    stem = _obj_stem(path)
+    rows = {"v": [], "vt": [], "vn": [], "f": []}
+    mtl = None
+    with open(stem + ".obj") as f:
+        for line in f:
+            words = line.split()
+            if not words or words[0].startswith("#"):
+                continue
+            if words[0] == "mtllib":
+                mtl = words[1]
+            elif words[0] in rows:
+                rows[words[0]].append(words[1:])
+    v = np.array(rows["v"], dtype=np.float64).astype(np.float32).reshape(-1, 3)
+    vt = np.array(rows["vt"], dtype=np.float64).astype(np.float32).reshape(-1, 2)
+    vn = np.array(rows["vn"], dtype=np.float64).astype(np.float32).reshape(-1, 3) if rows["vn"] else None
+    if any(len(face) != 3 for face in rows["f"]):
+        raise ValueError(f"{stem}.obj: non-triangular face")
+    corners = np.array([[c.split("/") for c in face] for face in rows["f"]], dtype=np.int64).reshape(len(rows["f"]), 3, -1)
+    if corners.shape[2] < 2 and len(corners):
+        raise ValueError(f"{stem}.obj: faces without texture coordinates")
+    tri = (corners[:, :, 0] - 1).astype(np.int32) if len(corners) else np.zeros((0, 3), np.int32)
+    uv = vt[corners[:, :, 1] - 1] if len(corners) else np.zeros((0, 3, 2), np.float32)
+    if vn is not None and len(corners) and not (corners[:, :, 2] == corners[:, :, 0]).all():
+        raise ValueError(f"{stem}.obj: normals are read per vertex (f a/ta/a)")
+    texture = None
+    if mtl is not None:
+        with open(os.path.join(os.path.dirname(stem), mtl)) as f:
+            maps = [line.split()[1] for line in f if line.split()[:1] == ["map_Kd"]]
+        if maps:
+            texture = np.asarray(Image.open(os.path.join(os.path.dirname(stem), maps[0])).convert("RGB"))
+    return {"vertices": v, "triangles": tri, "uv": uv, "normals": vn, "texture": texture}
+
+
 _PLY_TYPES = {b"char": "i1", b"int8": "i1", b"uchar": "u1", b"uint8": "u1", b"short": "<i2", b"int16": "<i2", b"ushort": "<u2", b"uint16": "<u2",
               b"int": "<i4", b"int32": "<i4", b"uint": "<u4", b"uint32": "<u4", b"float": "<f4", b"float32": "<f4", b"double": "<f8",
               b"float64": "<f8"}
@@ -321,9 +408,16 @@ def save_validation_outputs(base_exp_dir, outputs, inputs, tag, image_tag=None, 
     not hit the surface are black.
     outputs["fused_points"] (validate's surface_fusion), where present, is written as pcd/{scene}_{tag}.ply (write_point_cloud) in world
     coordinates (transform_vertices / transform_normals with scale_mat), with fused_normals and fused_colors where present; colours of points
-    no source view sees (fused_seen False) are written mid-grey.  Copied to pcd/scan{n}.ply it is what evaluate_dtu(mode="pcd") reads."""
+    no source view sees (fused_seen False) are written mid-grey.  Copied to pcd/scan{n}.ply it is what evaluate_dtu(mode="pcd") reads.
+    outputs["texture"] (validate's mesh_texture), where present, is written with the mesh as meshes/{scene}_{tag}.obj, its .mtl and its
+    .png beside the PLY (write_obj), in world coordinates, with outputs["texture_uv"] and the vertex normals where present; texels no
+    source view sees (outputs["texture_seen"] False) are mid-grey.  Not together with clean=True (ValueError before anything is written):
+    cleaning drops faces and the atlas is indexed by face, so texture the cleaned mesh afterwards (ImplicitSurface.texture_mesh)."""
     if clean_frustum and not clean:
         raise ValueError("save_validation_outputs: clean_frustum=True needs clean=True")
+    if clean and outputs.get("texture") is not None:
+        raise ValueError("save_validation_outputs: clean=True drops faces and the texture atlas is indexed by face: clean the mesh, then "
+                         "texture it with ImplicitSurface.texture_mesh")
     scene = inputs["scene"]
     image_tag = inputs["file_name"] if image_tag is None else image_tag
     vertices, triangles = outputs["vertices"], outputs["triangles"]
@@ -344,6 +438,10 @@ def save_validation_outputs(base_exp_dir, outputs, inputs, tag, image_tag=None, 
         os.makedirs(os.path.join(base_exp_dir, sub), exist_ok=True)
     paths["mesh"] = os.path.join(base_exp_dir, "meshes", f"{scene}_{tag}.ply")
     write_ply(paths["mesh"], vertices, triangles, normals=normals, colors=colors)
+    if outputs.get("texture") is not None:
+        paths["obj"], paths["mtl"], paths["texture"] = write_obj(os.path.join(base_exp_dir, "meshes", f"{scene}_{tag}.obj"), vertices, triangles,
+                                                                 outputs["texture_uv"], outputs["texture"], normals=normals,
+                                                                 seen=outputs.get("texture_seen"))
     paths["img"] = os.path.join(base_exp_dir, "val_img", f"{image_tag}_{tag}.png")
     Image.fromarray(outputs["img_fine"].astype(np.uint8)).save(paths["img"])
     paths["normal"] = os.path.join(base_exp_dir, "val_normal", f"{image_tag}_{tag}.png")

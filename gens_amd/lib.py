@@ -236,6 +236,11 @@ SIGNATURES = {
     "gens_cluster_keys": [_p, _l, _d, _d, _d, _d, _p, _p],
     "gens_cluster_triangles": [_p, _l, _p, _l, _p, _p, _p, _p],
     "gens_cluster_solve": [C.POINTER(ClusterSolveArgs), _p],
+    "gens_texture_points": [_p, _l, _p, _l, _i, _l, _l, _p, _p, _p],
+    "gens_texture_snap": [_p, _p, _p, _p, _d, _f, _l, _p, _p],
+    "gens_texture_keep_better": [_p, _p, _p, _p, _p, _p, _f, _l, _p, _p],
+    "gens_texture_pack": [_p, _p, _i, _l, _i, _l, _l, _p, _p, _p],
+    "gens_texture_uv": [_l, _i, _p, _p],
 }
 
 _lib = None

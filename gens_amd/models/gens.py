@@ -109,6 +109,9 @@ class GenS(nn.Module):
         simplify = confs.get("mesh_simplify", None)             # optional: extract_geometry / validate simplify the mesh on the device (ops.simplify_mesh, K33); a cell edge in lattice spacings
         if simplify is not None:
             self.implicit_surface.mesh_simplify = float(simplify)
+        texture = confs.get("mesh_texture", None)               # optional: extract_geometry / validate also return a texture atlas of the mesh (texture_mesh, K34); the tile edge in texels or its keywords
+        if texture is not None:
+            self.implicit_surface.mesh_texture = dict(texture) if hasattr(texture, "keys") else texture
         lipschitz = confs.get("lattice_lipschitz", None)        # optional: the bound that lattice assumes (ImplicitSurface.lattice_lipschitz)
         if lipschitz is not None:
             self.implicit_surface.lattice_lipschitz = float(lipschitz)

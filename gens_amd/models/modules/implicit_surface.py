@@ -17,6 +17,8 @@ Same constructor, method names, argument order and output keys as the reference,
 unchanged.  Host RNG draws (`torch.rand([B,1])`, `torch.rand([1024,3])` from the CPU generator, :256,:362) are
 kept in the reference's order so a seeded run renders the same jitter.
 """
+import math
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -592,6 +594,136 @@ class ImplicitSurface(nn.Module):
             raise ValueError("simplify = True: pass the cell edge in lattice spacings (a positive number; None, False or 0: off)")
         return ops.simplify_request("simplify", simplify)[0]
 
+    mesh_texture = None            # the tile edge in texels (3 to 64), or a dict of texture_mesh's keywords (texels, snap, max_move, chunk):
+                                   # extract_geometry / validate also return a texture atlas of the mesh (texture_mesh, K34).  None / False / 0:
+                                   # off
+    last_texture_stats = None      # H, W, samples, the unseen share and the snap counts of the last texture_mesh call
+    _TEXTURE_KEYS = ("texels", "snap", "max_move", "threshold", "chunk")
+
+    def _texture_option(self, texture):
+        """The texture a mesh call asks for (None: the attribute `mesh_texture`) -> a dict of texture_mesh's keywords, or None for off (None,
+        False, 0).  An integer is the tile edge `texels`.  ValueError for anything else."""
+        texture = self.mesh_texture if texture is None else texture
+        if texture is None or texture is False or (not isinstance(texture, bool) and isinstance(texture, (int, float)) and texture == 0):
+            return None
+        if isinstance(texture, dict):
+            unknown = [k for k in texture if k not in self._TEXTURE_KEYS]
+            if unknown:
+                raise ValueError(f"texture: unknown keywords {unknown!r} (texture_mesh takes {self._TEXTURE_KEYS!r})")
+            return dict(texture)
+        if isinstance(texture, bool) or not isinstance(texture, (int, np.integer)):
+            raise ValueError(f"texture = {texture!r}: the tile edge in texels (an integer from {ops.TEXTURE_MIN_TEXELS} to {ops.TEXTURE_MAX_TEXELS}), "
+                             "a dict of texture_mesh's keywords, or None / False / 0 for off")
+        return {"texels": int(texture)}
+
+    def _texture_request(self, n_faces, volumes, views, texels=8, snap=0, max_move=None):
+        """texture_mesh's arguments, checked before anything is launched -> (texels, snap, max_move).  n_faces: the face count, or None where
+        the mesh does not exist yet (extract_geometry checks the rest first and the atlas once the mesh is known).  The limits on networks
+        and views are _attribute_request's for "colors" (and for "normals" with a snap, which needs the gradient)."""
+        ops.texture_layout(0, texels)                  # (ValueError for texels that is not an integer from 3 to 64)
+        s = int(texels)
+        if isinstance(snap, bool) or not isinstance(snap, (int, np.integer)) or snap < 0:
+            raise ValueError(f"texture_mesh: snap = {snap!r}: the number of Newton rounds, an integer >= 0")
+        if max_move is not None:
+            if isinstance(max_move, bool) or not isinstance(max_move, (int, float, np.integer, np.floating)) or not float(max_move) > 0.0:
+                raise ValueError(f"texture_mesh: max_move = {max_move!r}: a positive length (None: the longest edge of the texel's triangle)")
+            max_move = float(max_move)
+        if views is None:
+            raise ValueError("texture_mesh needs the scene's views (views=scene.views): the colour is a function of the point and the views")
+        self._attribute_request(("normals", "colors") if snap else ("colors",), volumes, views)
+        if n_faces is not None:
+            h, w = ops.texture_layout(n_faces, s)[:2]
+            if h > ops.TEXTURE_MAX_EDGE or w > ops.TEXTURE_MAX_EDGE:
+                fit = ops.texture_fit(n_faces)
+                raise ValueError(f"texture_mesh: {n_faces} faces at texels = {s} need an atlas of {h} x {w} pixels, above {ops.TEXTURE_MAX_EDGE} a side; "
+                                 + (f"the largest texels that fits is {fit}" if fit is not None else "no tile edge fits")
+                                 + "; reduce the mesh first (extract_geometry(simplify=), ops.simplify_mesh)")
+        return s, int(snap), max_move
+
+    @torch.no_grad()
+    def _texture_samples(self, pts, tri, vols, texels, snap, max_move, threshold, chunk):
+        """The points of every atlas sample of the device mesh (pts (V, 3) float32, tri (T, 3) int32), after `snap` guarded Newton rounds ->
+        (points (T P, 3) float32 on the device, steps skipped, steps turned back).  Per chunk snap + 1 value + gradient evaluations: each
+        round's evaluation is also the guard of the round before (ops.texture_keep_better), and one more guards the last.  They run through
+        _lattice_passes(want_grad=True): a split-half overflow repeats all of it from the unsnapped points in float32."""
+        if not snap or not tri.shape[0]:
+            return ops.texture_points(pts, tri, texels), 0, 0
+        chunk = max(1, int(chunk))
+        if self._fused_plan(vols) is None:
+            raise ValueError("texture_mesh: snap needs the fused SDF kernels; these volumes do not take them")
+
+        def run(evaluate):
+            if max_move is None:
+                samples, limit = ops.texture_points(pts, tri, texels, with_edge=True)
+            else:
+                samples, limit = ops.texture_points(pts, tri, texels), None
+            skipped = torch.zeros((), device=samples.device, dtype=torch.int64)
+            reverted = torch.zeros((), device=samples.device, dtype=torch.int64)
+            for s in range(0, samples.shape[0], chunk):
+                e = min(s + chunk, samples.shape[0])
+                p, origin = samples[s:e], None
+                for k in range(snap + 1):
+                    sdf, grad = evaluate(p)[:2]
+                    sdf = sdf.reshape(-1)
+                    if origin is not None:                 # the step that led here did not lower |g|: back to its origin, with that state
+                        reverted += ops.texture_keep_better(p, sdf, grad, *origin, threshold).sum()
+                    if k == snap:
+                        break
+                    origin = (p.clone(), sdf, grad)
+                    taken = ops.texture_snap(p, sdf, grad, threshold, limit=None if limit is None else limit[s:e], max_move=max_move)
+                    skipped += (e - s) - taken.sum()
+            return samples, skipped, reverted
+
+        samples, skipped, reverted = self._lattice_passes(vols, None, run, want_grad=True)
+        return samples, int(skipped), int(reverted)
+
+    @torch.no_grad()
+    def texture_mesh(self, points, triangles, volumes, views, texels=8, snap=0, max_move=None, threshold=0.0, chunk=1 << 21):
+        """A texture atlas for a triangle mesh in the model's frame (K34): points (V,3) and triangles (T,3), numpy or
+        tensors, from anywhere -- an extracted mesh, a simplified or cleaned one, a file (the points are evaluated as float32).  Every
+        triangle gets texels (texels + 1) / 2 texels of an image whose resolution does not depend on the face count; each texel is coloured
+        by the blending network at its point on the triangle, so the detail of the source images survives a coarse mesh.
+        -> dict of numpy arrays: "texture" (H,W,3) uint8 (row 0 at the top; validate's img_fine convention, K30's rule), "texture_seen" (H,W)
+        bool (some source view has the texel's point in its frustum; elsewhere, and where no triangle owns the texel, the colour is
+        arbitrary / 0 and writers use mid-grey) and "texture_uv" (T,3,2) float32, one coordinate pair per corner, origin bottom-left
+        (io.write_obj writes all three).  The layout is ops.texture_layout's: H = rows texels by W = cols (texels + 1).
+        snap (default 0): Newton rounds that move each texel's point towards the surface sdf + threshold = 0 before it is coloured, for
+        simplified meshes, whose faces are chords of the surface (a point off the surface projects into the source views with parallax).
+        A step longer than max_move (default: the longest edge of the texel's triangle), or with a value or gradient that is not finite,
+        is skipped, and a step after which |g| is not lower (as the evaluator sees it: each round's evaluation checks the round before,
+        one more checks the last) is turned back, so no point ends with a larger |g| than it began with.  One or two rounds of Newton's
+        method: NOTHING else is promised about convergence; self.last_texture_stats counts the skipped and the turned-back steps.  chunk: points per network launch; the result does not depend on it.
+        Bilinear filtering inside a triangle reads that triangle's texels only.  Not promised: anything under mip-mapping, and seam-free
+        colour across triangle edges (two triangles sample a shared edge at the same points only up to their different extrapolations).
+        ValueError before any launch (_texture_request): texels outside 3 .. 64, snap < 0, max_move <= 0, an atlas edge above 16 384 pixels,
+        missing views, or networks outside the fused kernels.  self.last_texture_stats: "H", "W", "samples", "unseen" (the share of owned
+        texels no view sees), "snap", "snap_skipped", "snap_reverted"."""
+        tri_host = triangles.detach() if torch.is_tensor(triangles) else np.asarray(triangles)
+        if tri_host.ndim != 2 or tri_host.shape[1] != 3:
+            raise ValueError(f"texture_mesh: triangles are {tuple(tri_host.shape)}, expected (T, 3)")
+        n_faces = int(tri_host.shape[0])
+        texels, snap, max_move = self._texture_request(n_faces, volumes, views, texels, snap, max_move)
+        if not math.isfinite(float(threshold)):
+            raise ValueError(f"texture_mesh: threshold = {threshold!r} (finite)")
+        vols = volumes if isinstance(volumes, ops.VolumeSet) else ops.VolumeSet.packed(volumes)
+        dev = vols.tensors[0].device
+        pts = torch.as_tensor(points).detach().reshape(-1, 3).to(device=dev, dtype=torch.float32).contiguous()
+        tri = torch.as_tensor(tri_host).to(device=dev, dtype=torch.int32).contiguous()
+        if n_faces and (int(tri.min()) < 0 or int(tri.max()) >= pts.shape[0]):
+            raise ValueError(f"texture_mesh: triangle indices {int(tri.min())} .. {int(tri.max())} outside the {pts.shape[0]} vertices")
+        h, w, _, _, per_face = ops.texture_layout(n_faces, texels)
+        atlas = torch.zeros(h, w, 3, device=dev, dtype=torch.uint8)
+        seen = torch.zeros(h, w, device=dev, dtype=torch.uint8)
+        samples, skipped, reverted = self._texture_samples(pts, tri, vols, texels, snap, max_move, float(threshold), chunk)
+        self._point_chain(samples, vols, views, False, True, chunk, lambda s, e, grad, rgb, vis: ops.texture_pack(
+            rgb, vis, n_faces, texels, s, e, atlas=atlas, seen=seen))
+        uv = ops.texture_uv(n_faces, texels, dev)
+        out = {"texture": atlas.cpu().numpy(), "texture_seen": seen.cpu().numpy().astype(bool), "texture_uv": uv.cpu().numpy()}
+        n = n_faces * per_face
+        self.last_texture_stats = {"H": h, "W": w, "samples": n, "unseen": 1.0 - float(out["texture_seen"].sum()) / n if n else 0.0,
+                                   "snap": snap, "snap_skipped": skipped, "snap_reverted": reverted}
+        return out
+
     def _lattice_route(self, sparse, sparse_mesh, shard):
         """The options of sdf_grid (sparse_mesh=False) and extract_geometry -> (route, brick edge): "dense" (the dense lattice, brick None),
         "lattice" (ops.sparse_lattice, K28) or "mesh" (ops.brick_marching_cubes, K29).  None = the attribute of that name; sparse False =
@@ -988,7 +1120,7 @@ class ImplicitSurface(nn.Module):
         return out
 
     def extract_geometry(self, volumes, bound_min, bound_max, resolution, threshold, shard=None, sparse=None, sparse_mesh=None, attributes=None,
-                         views=None, simplify=None):
+                         views=None, simplify=None, texture=None):
         """-> vertices (V,3) float64, triangles (T,3) int32 as numpy arrays (implicit_surface.py:407-427).  The SDF lattice and
         the marching cubes both run on the device (the reference: 512 D2H copies + PyMCubes on the host); only the mesh is copied.
         sparse: sdf_grid's option of that name, with this call's threshold.  sparse_mesh (default: the attribute of that name, None = off):
@@ -1005,9 +1137,19 @@ class ImplicitSurface(nn.Module):
         the attribute pass (normals and colours are evaluated at the new vertices, not carried) and before the copy to the host; with a shard,
         on every rank that holds the gathered mesh.  self.last_simplify_stats: its counts (None when off).  Topology is not preserved and no
         distance to the surface is promised.  ValueError before any launch for a cell edge that is not a positive
-        finite number."""
+        finite number.
+        texture (default: the attribute `mesh_texture`; None, False or 0 = off): the tile edge in texels (3 to 64) or a dict of texture_mesh's
+        keywords (texels, snap, max_move, chunk) -> a further result after the attribute dict (whose place holds None when only the
+        texture is asked for): texture_mesh's dict for the returned mesh (K34), computed after marching cubes and
+        the simplification on the device-resident mesh, where the attribute pass runs (with a shard, on every rank that holds the gathered
+        mesh); this call's threshold unless the dict names one.  views is needed.  ValueError before any launch for what _texture_request
+        refuses; the atlas edge (at most 16 384 pixels) can only be checked once the mesh exists, before any texture launch."""
         attributes = self._attribute_request(attributes, volumes, views)
         simplify = self._simplify_request(simplify)
+        texture = self._texture_option(texture)
+        if texture is not None:
+            texture = {"threshold": threshold, **texture}
+            self._texture_request(None, volumes, views, *(texture.get(k, d) for k, d in (("texels", 8), ("snap", 0), ("max_move", None))))
         self.last_simplify_stats = None
         route, brick = self._lattice_route(sparse, sparse_mesh, shard)
         mesh = None
@@ -1021,24 +1163,29 @@ class ImplicitSurface(nn.Module):
         else:
             u = self.sdf_grid(volumes, bound_min, bound_max, resolution, shard=shard, sparse=sparse, threshold=threshold)
             if u is None:
-                return (None, None, None) if attributes else (None, None)
+                return (None,) * (4 if texture is not None else 3 if attributes else 2)
             mesh = ops.marching_cubes(u, threshold)
         vertices, triangles = mesh
         if simplify is not None:
             vertices, triangles, _, self.last_simplify_stats = ops.simplify_mesh(vertices, triangles, simplify, origin=(-0.5, -0.5, -0.5))
         b_max, b_min = bound_max.detach().cpu().numpy(), bound_min.detach().cpu().numpy()
-        attrs = None
-        if attributes:                                 # on the device-resident vertices; span: the host expression's (float32) difference, widened
+        attrs = tex = None
+        if attributes or texture is not None:          # on the device-resident vertices; span: the host expression's (float32) difference, widened
             points = ops.vertex_points(vertices, resolution, (b_max - b_min).astype(np.float64).tolist(), b_min.astype(np.float64).tolist())
+        if attributes:
             attrs = self.vertex_attributes(points, volumes, views, attributes)
+        if texture is not None:
+            tex = self.texture_mesh(points, triangles, volumes, views, **texture)
         vertices, triangles = vertices.cpu().numpy(), triangles.cpu().numpy()
         vertices = vertices / (resolution - 1.0) * (b_max - b_min)[None, :] + b_min[None, :]
+        if texture is not None:
+            return vertices, triangles, attrs, tex
         return (vertices, triangles, attrs) if attributes else (vertices, triangles)
 
     @torch.no_grad()
     def validate(self, rays_o, rays_d, near, far, volumes, mask_volumes, imgs, features, match_features, intrs, c2ws, bound_min, bound_max,
                  hw, cos_anneal_ratio=1.0, step=None, extract_geometry=True, mesh_resolution=512, threshold=0.0, scene=None, shard=None, sparse=None,
-                 sparse_mesh=None, mesh_attributes=None, surface_render=None, surface_fusion=None, mesh_simplify=None):
+                 sparse_mesh=None, mesh_attributes=None, surface_render=None, surface_fusion=None, mesh_simplify=None, mesh_texture=None):
         """shard (gens_amd.distributed.Shard, optional): render only this rank's contiguous ray range and evaluate only its lattice
         chunks; the (P, 8) image buffer / the lattice slabs are gathered over RCCL, so every rank returns the whole image.  The jitter
         of EVERY ray is drawn on every rank from the identically seeded CPU generator (the reference's draw order) and sliced with
@@ -1051,9 +1198,13 @@ class ImplicitSurface(nn.Module):
         and views) is traced to the surface and the depth maps are fused into a point cloud (fuse_surface, K32) -> outputs["fused_points"],
         ["fused_normals"], ["fused_colors"], ["fused_seen"]; not with a shard.  mesh_simplify: extract_geometry's `simplify` (a cell edge in
         lattice spacings; default: the attribute of that name, None / False / 0 = off): outputs["vertices"], ["triangles"] and the vertex
-        attributes are those of the simplified mesh (K33); self.last_simplify_stats holds its counts."""
+        attributes are those of the simplified mesh (K33); self.last_simplify_stats holds its counts.  mesh_texture: extract_geometry's
+        `texture` with this scene's views (the tile edge in texels or a dict of texture_mesh's keywords; default: the attribute of that name,
+        None / False / 0 = off) -> outputs["texture"], ["texture_seen"], ["texture_uv"] (K34), which save_validation_outputs writes as an
+        OBJ beside the PLY."""
         outputs = {}
         mesh_simplify = self._simplify_request(mesh_simplify) if extract_geometry else None      # (refused before anything is launched)
+        mesh_texture = self._texture_option(mesh_texture) if extract_geometry else None
         surface_fusion = self.surface_fusion if surface_fusion is None else surface_fusion
         if surface_fusion:
             if shard is not None:
@@ -1085,10 +1236,11 @@ class ImplicitSurface(nn.Module):
             t_geo = time.perf_counter()
             mesh = self.extract_geometry(scene.volumes_nograd(), bound_min, bound_max, mesh_resolution, threshold, shard=shard, sparse=sparse,
                                          sparse_mesh=sparse_mesh, attributes=mesh_attributes, views=scene.views,
-                                         simplify=0 if mesh_simplify is None else mesh_simplify)
+                                         simplify=0 if mesh_simplify is None else mesh_simplify, texture=0 if mesh_texture is None else mesh_texture)
             outputs["vertices"], outputs["triangles"] = mesh[0], mesh[1]
-            for name, values in ((mesh[2] or {}) if len(mesh) == 3 else {}).items():
+            for name, values in ((mesh[2] or {}) if len(mesh) >= 3 else {}).items():
                 outputs["vertex_" + name] = values
+            outputs.update(mesh[3] or {} if len(mesh) == 4 else {})
             self.last_geometry_s = time.perf_counter() - t_geo     # (ends with the mesh's read-back: wall time is the item's share; bench.py's default_path)
         # one (P, 8) device buffer [rgb | normal | sdf_depth | render_depth] filled chunk by chunk: ONE D2H copy per image
         # into a pinned host buffer (the reference copies 4 tensors per 256-ray chunk, implicit_surface.py:446-453)

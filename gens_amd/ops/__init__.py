@@ -28,6 +28,7 @@ is what it was when ops was one module:
     ops.trace     K31: sphere tracing of the surface along rays (sphere_trace) and the per-ray depth / normal / colour pack (surface_pack).
     ops.fusion    K32: per-view depth maps fused into a consistency-filtered point cloud (fusion_cams, fuse_depth_maps, fused_points).
     ops.simplify  K33: mesh simplification by vertex clustering with quadric-optimal representatives (simplify_mesh).
+    ops.texture   K34: texture atlases for triangle meshes: atlas samples to points, the guarded Newton snap, colours to pixels, corner coordinates.
 """
 from .base import *  # noqa: F401,F403
 from .volume import *  # noqa: F401,F403
@@ -48,3 +49,4 @@ from .vertex_attrs import *  # noqa: F401,F403
 from .trace import *  # noqa: F401,F403
 from .fusion import *  # noqa: F401,F403
 from .simplify import *  # noqa: F401,F403
+from .texture import *  # noqa: F401,F403

@@ -65,7 +65,8 @@ const char* gens_last_error(void);
  *       gens_brick_coarse_points, gens_brick_points, gens_brick_active, gens_brick_emit_flags, gens_brick_mc_classify, gens_brick_mc_emit,
  *       and K30's gens_vertex_points, gens_vertex_pack, and K31's gens_trace_begin, gens_trace_march, gens_trace_refine, gens_trace_gather,
  *       gens_surface_pack, and K32's gens_fuse_depth_maps, gens_fused_points, and K33's gens_cluster_keys, gens_cluster_triangles,
- *       gens_cluster_solve. */
+ *       gens_cluster_solve, and K34's gens_texture_points, gens_texture_snap, gens_texture_keep_better,
+ *       gens_texture_pack, gens_texture_uv. */
 int gens_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -1116,6 +1117,67 @@ int gens_cluster_keys(const double* vertices, int64_t n_vertices, double origin_
 int gens_cluster_triangles(const int32_t* triangles, int64_t n_triangles, const int32_t* vertex_cluster, int64_t n_vertices, int32_t* ranks,
                            uint8_t* survive, int32_t* triple, void* stream);
 int gens_cluster_solve(const gens_cluster_solve_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * K34  Texture atlases for triangle meshes (ops.texture_points / texture_snap / texture_pack / texture_uv, ImplicitSurface.texture_mesh,
+ *      extract_geometry(texture=)), csrc/k34_mesh_texture.hip.  tests/mesh_texture_reference.py restates all of it in numpy.
+ *
+ *   Definition.  Arithmetic is float64 from the float32 inputs, every operation rounded on its own, in the order written; results are
+ *   rounded once to float32.
+ *     Inputs: points (V, 3) float32 in the model's frame, triangles (T, 3) int32, texels = S, an integer with 3 <= S <= 64 (the tile edge).
+ *     1. Layout.  Every triangle gets P = S (S + 1) / 2 texels.  Triangle f lives in tile f >> 1, half f & 1.  A tile is S + 1 columns by S
+ *        rows.  With n_tiles = ceil(T / 2):  cols = ceil(sqrt(n_tiles)) in exact integers, rows = ceil(n_tiles / cols) (both 0 for T = 0).
+ *        The atlas is H = rows S by W = cols (S + 1), uint8 RGB, row 0 at the top; tile q sits at tile column q % cols and tile row q / cols.
+ *     2. Texels.  The local texels of a triangle are (i', j') with i', j' >= 0 and i' + j' <= S - 1.  Sample number k = 0 .. P - 1
+ *        enumerates them with j' as the outer and i' as the inner index (row j' holds S - j' texels); sample s = f P + k.  Half 0 maps
+ *        (i', j') to the tile-local column and row (i, j) = (i', j'), half 1 to (S - i', S - 1 - j'), a half turn: half 0 takes i + j <= S - 1,
+ *        half 1 takes i + j >= S, so every texel of a tile belongs to exactly one triangle.  The pixel of a texel is
+ *        x = (q % cols) (S + 1) + i,  y = (q / cols) S + j.
+ *     3. Points.  With A, B, C the triangle's corners in stored order, a = i' / (S - 2) and b = j' / (S - 2):
+ *        p = (A + a (B - A)) + b (C - A), component by component.  The corners sit at the local texels (0, 0), (S - 2, 0) and (0, S - 2),
+ *        where p is A, B and C.  Texels with i' + j' = S - 1 lie just outside the triangle, on its plane: they exist so that bilinear
+ *        filtering at any point of the triangle reads this triangle's texels only.  A triangle with an index outside 0 .. V - 1 has NaN
+ *        points (the index is never read through).  Longest edge of a triangle (the default step limit of 5): with
+ *        e(P, Q) = ((Q_x - P_x)^2 + (Q_y - P_y)^2) + (Q_z - P_z)^2:  m = e(A, B); if e(B, C) > m, m = e(B, C); if e(C, A) > m, m = e(C, A);
+ *        the edge is sqrt(m) rounded to float32 (NaN for a triangle with a bad index).
+ *     4. Corner coordinates.  With (x, y) the pixel of a corner's texel:  u = (x + 0.5) / W,  v = 1 - (y + 0.5) / H (origin bottom-left, as
+ *        OBJ expects) -> uv (T, 3, 2) float32.
+ *     5. Optional snap, one round:  g = sdf + threshold (K31's g),  n2 = (gx^2 + gy^2) + gz^2,  t = g / n2,  step = t grad per component,
+ *        len2 = (step_x^2 + step_y^2) + step_z^2.  The step is taken, p_a <- p_a - step_a (float32 state), iff g and n2 are finite, n2 > 0
+ *        and len2 <= limit limit, with limit the sample's own (a float32, widened) or one max_move for all.  Otherwise p is kept.
+ *        The guard: value and gradient are evaluated again at the new point (the next round's evaluation, and one more after the last
+ *        round), and where |g| there is not <= |g| at the step's origin (a NaN included) the point goes back to the origin with the
+ *        origin's value and gradient -- a later round repeats that step and is turned back again.  So no point ends with a larger |g|
+ *        than it began with, as the evaluator sees it.  Nothing else is promised about convergence.
+ *     6. Colour: K30's rule (csrc/pack_rules.h): trunc(clip(256 c, 0, 255)), 0 where c is not finite; seen = some source view has the point
+ *        in its frustum.  Texels no triangle owns (the tail of the last tile row, the second half of the last tile when T is odd) are not
+ *        written: callers zero the atlas and the seen plane first.
+ *   NOT promised: anything under mip-mapping (tiles have no gutters wider than the one texel row), and seam-free colour across triangle
+ *   edges (two triangles sample the same edge at the same points only up to their different extrapolations).
+ *
+ *   gens_texture_points: one thread per sample of [s0, s1) (a chunk may begin and end inside a triangle) -> out (s1 - s0, 3) float32 and,
+ *     if edge is not NULL, edge (s1 - s0) float32 (the longest edge of the sample's triangle).
+ *   gens_texture_snap: one thread per sample: points (n, 3) float32 in place, value (n) float32 = sdf, grad (n, 3) float32, limit (n)
+ *     float32 or NULL (then max_move > 0 applies to all) -> taken (n) uint8 (1 where the step was taken).
+ *   gens_texture_keep_better: one thread per sample: where |value + threshold| <= |prev_value + threshold| is false, points (n, 3), value (n)
+ *     and grad (n, 3) are overwritten, in place, with prev_points, prev_value and prev_grad -> reverted (n) uint8.
+ *   gens_texture_pack: color (s1 - s0, 3) float32 and vis (s1 - s0, n_src) uint8 of samples [s0, s1) -> the three bytes of each sample's
+ *     texel in atlas (H, W, 3) uint8 and its flag in seen (H, W) uint8, written by one thread with byte stores (no two samples share a pixel).
+ *   gens_texture_uv: one thread per triangle -> uv (n_faces, 3, 2) float32.
+ *   All pointers are device pointers.  Arguments are checked before any launch: texels outside 3 .. 64, negative sizes, a sample range
+ *   outside 0 .. T P, n_src outside 1 .. 255, a threshold that is not finite, no limit and max_move not positive, null pointers:
+ *   GENS_EINVAL; V, T or the samples of one launch >= 2^31: GENS_ELIMIT.  An empty range, n == 0 and T == 0 succeed without a launch.
+ *   The ABI version stays 12: no existing entry changes.
+ * ---------------------------------------------------------------------------------------------------------- */
+int gens_texture_points(const float* points, int64_t n_vertices, const int32_t* triangles, int64_t n_faces, int texels, int64_t s0, int64_t s1,
+                        float* out, float* edge, void* stream);
+int gens_texture_snap(float* points, const float* value, const float* grad, const float* limit, double max_move, float threshold, int64_t n,
+                      uint8_t* taken, void* stream);
+int gens_texture_keep_better(float* points, float* value, float* grad, const float* prev_points, const float* prev_value, const float* prev_grad,
+                             float threshold, int64_t n, uint8_t* reverted, void* stream);
+int gens_texture_pack(const float* color, const uint8_t* vis, int n_src, int64_t n_faces, int texels, int64_t s0, int64_t s1, uint8_t* atlas,
+                      uint8_t* seen, void* stream);
+int gens_texture_uv(int64_t n_faces, int texels, float* uv, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K14  C (m x n) = A^T B for tall row-major operands A (k x m), B (k x n), k >> m, n: the weight-gradient product of the training
