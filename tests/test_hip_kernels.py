@@ -167,18 +167,19 @@ def test_k3_ray_points_vs_oracle(ops):
     sc = synthetic.make_scene(nv=3, h=48, w=64, n_levels=1, seed=4)
     ro, rd = synthetic.make_rays(sc["intrs"], sc["c2ws"], 48, 64, step=4)
     masks = [(torch.rand(1, 1, d, d, d, generator=g) > 0.4).float() for d in (32, 16, 8)]
-    z = torch.sort(torch.rand(ro.shape[0], 37, generator=g) * 2.2 + 1.1, -1)[0]
-    for mid in (False, True):
-        if mid:
-            dist = torch.cat([z[:, 1:] - z[:, :-1], torch.full((z.shape[0], 1), 1 / 32)], -1)
-            zz = z + dist * 0.5
-        else:
-            zz = z
-        ref_pts = (ro[:, None] + rd[:, None] * zz[..., None]).reshape(-1, 3)
-        pts, valid = ops.ray_points(dev(ro), dev(rd), dev(z), dev(masks), mid=mid, sample_dist=1 / 32)
-        close(pts, ref_pts, atol=1e-6, what="pts")
-        ref_valid = K.point_valid(masks, pts.cpu())
-        assert torch.equal(valid.cpu(), ref_valid)
+    for n in (37, 64, 128):            # 37: ray and sample index by division; 64 and 128: by shift and mask
+        z = torch.sort(torch.rand(ro.shape[0], n, generator=g) * 2.2 + 1.1, -1)[0]
+        for mid in (False, True):
+            if mid:
+                dist = torch.cat([z[:, 1:] - z[:, :-1], torch.full((z.shape[0], 1), 1 / 32)], -1)
+                zz = z + dist * 0.5
+            else:
+                zz = z
+            ref_pts = (ro[:, None] + rd[:, None] * zz[..., None]).reshape(-1, 3)
+            pts, valid = ops.ray_points(dev(ro), dev(rd), dev(z), dev(masks), mid=mid, sample_dist=1 / 32)
+            close(pts, ref_pts, atol=1e-6, what=f"pts n={n}")
+            ref_valid = K.point_valid(masks, pts.cpu())
+            assert torch.equal(valid.cpu(), ref_valid)
 
 
 # --------------------------------------------------------------------------------------------------- K4
@@ -224,13 +225,18 @@ def test_k5_k7_golden(ops, golden):
 
 def test_k7_merge_with_sdf_and_ties_vs_oracle(ops):
     g = torch.Generator().manual_seed(11)
-    for n, n_new in ((64, 16), (112, 16), (5, 3), (100, 28)):
+    for n, n_new in ((64, 16), (112, 16), (5, 3), (100, 28), (64, 64), (127, 1), (1, 64), (63, 2)):
         z = torch.sort(torch.rand(9, n, generator=g), -1)[0]
         zn = torch.sort(torch.rand(9, n_new, generator=g), -1)[0]
-        zn[0, :2] = z[0, 3]            # ties between old and new, and among new
+        zn[0, :2] = z[0, min(3, n - 1)]   # ties between old and new, and among new
         zn[1] = z[1, -1] + 1.0         # all new samples after the last old one
         zn[2] = z[2, 0] - 1.0          # all before
         zn[0] = torch.sort(zn[0])[0]
+        if (n, n_new) == (63, 2):      # a tie across the two register slots of a lane: the last old sample (merged index 62) and a new one (63)
+            zn[3, 0], zn[3, 1] = z[3, 62], z[3, 62] + 0.1
+        if n >= 64:                    # and one between old sample 63 and a new one, which lands on merged index 64 or later
+            zn[4, 0] = z[4, 63]
+            zn[4] = torch.sort(zn[4])[0]
         s, sn = torch.randn(9, n, generator=g), torch.randn(9, n_new, generator=g)
         rz, rs = K.merge_samples(z, zn, s, sn)
         oz, os_ = ops.merge_samples(dev(z), dev(zn), dev(s), dev(sn))
@@ -270,7 +276,9 @@ def test_bit_packed_masks_and_carried_validity_change_nothing(ops, golden):
 
 
 # --------------------------------------------------------------------------------------------------- K8
-def _composite_case(b, n, s, seed, smooth=True):
+def _composite_case(b, n, s, seed, smooth=True, placed=False):
+    """placed: the first valid sign change of ray r (r >= 2) sits at segment r mod (n - 1): both of its samples valid, the SDF positive up to
+    it (an invalid sample's 100 is positive too) and negative right behind it."""
     from gens_amd import synthetic
     g = torch.Generator().manual_seed(seed)
     sc = synthetic.make_scene(nv=s + 1, h=48, w=64, n_levels=1, seed=seed)
@@ -282,6 +290,13 @@ def _composite_case(b, n, s, seed, smooth=True):
     vm[0] = 0                       # a ray with no valid sample at all
     vm[1] = 1
     sdf = torch.linalg.norm(mid, dim=-1) - 0.55 + 0.03 * torch.randn(b, n, generator=g)
+    if placed:
+        rows, j = torch.arange(2, b), torch.arange(n)[None]
+        k = rows % (n - 1)
+        vm[rows, k] = 1
+        vm[rows, k + 1] = 1
+        mag = sdf[2:].abs().clamp_min(1e-3)
+        sdf[2:] = torch.where(j <= k[:, None], mag, torch.where(j == k[:, None] + 1, -mag, sdf[2:]))
     sdf = torch.where(vm > 0, sdf, torch.full_like(sdf, 100.0))
     grad = torch.nn.functional.normalize(mid, dim=-1) + 0.2 * torch.randn(b, n, 3, generator=g)
     grad = grad * vm[..., None]
@@ -291,9 +306,16 @@ def _composite_case(b, n, s, seed, smooth=True):
     return dict(ro=ro, rd=rd, z=z, sdf=sdf, grad=grad, col=col, sm=sm, vm=vm, vis=vis, c2w=sc["c2ws"][0])
 
 
-@pytest.mark.parametrize("n,cos_anneal,inv_s", [(128, 0.5, 20.0), (128, 1.0, 300.0), (70, 0.0, 64.0)])
+@pytest.mark.parametrize("n,cos_anneal,inv_s", [(128, 0.5, 20.0), (128, 1.0, 300.0), (70, 0.0, 64.0), (2, 0.5, 20.0), (64, 1.0, 64.0), (65, 0.5, 64.0)])
 def test_k8_composite_fwd_bwd_vs_oracle(ops, n, cos_anneal, inv_s):
-    c = _composite_case(b=37, n=n, s=3, seed=20 + n)
+    """n = 2, 64, 65: the smallest ray, a ray that fills the lower register slots exactly, and one sample more; 70 rays with the first valid sign
+    change of ray r placed at segment r mod (n - 1), so that at n = 65 ray 63 crosses between samples 63 and 64 -- pick2 across a lane's two
+    slots and the crossing index taken from the upper slots' ballot, forward and backward."""
+    if n in (2, 64, 65):
+        c = _composite_case(b=70, n=n, s=3, seed=20 + n, placed=True)
+        assert n < 65 or int(torch.argmax((c["sdf"][63, :-1] * c["sdf"][63, 1:] <= 0).float())) == 63
+    else:
+        c = _composite_case(b=37, n=n, s=3, seed=20 + n)
     leaf = lambda t: t.clone().requires_grad_(True)  # noqa: E731
     # oracle
     o_in = [leaf(c["sdf"]), leaf(c["grad"]), leaf(c["sm"]), leaf(c["col"]), torch.tensor(inv_s, requires_grad=True)]
@@ -303,6 +325,8 @@ def test_k8_composite_fwd_bwd_vs_oracle(ops, n, cos_anneal, inv_s):
     out = ops.composite(dev(c["ro"]), dev(c["rd"]), dev(c["z"]), 1 / 32, d_in[0], d_in[1], d_in[2], d_in[3], dev(c["vm"]) > 0,
                         dev(c["vis"]), d_in[4], cos_anneal, dev(c["c2w"]))
     b = c["z"].shape[0]
+    if n in (2, 64, 65):
+        assert torch.equal(out["cross_idx"][2:].cpu().long(), torch.arange(2, b) % (n - 1))      # the placed crossings, 63 among them at n = 65
     close(out["color"], ref["color_fine"], atol=2e-5, rtol=1e-4, what="color")
     close(out["normal"], ref["normal"], atol=2e-5, rtol=1e-4, what="normal")
     close(out["depth"], ref["render_depth"], atol=2e-5, rtol=1e-4, what="depth")
