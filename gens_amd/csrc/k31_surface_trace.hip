@@ -161,11 +161,6 @@ __global__ __launch_bounds__(256) void trace_gather_k(const float* __restrict__ 
     out[e] = (r >= 0 && r < n) ? points[3 * r + e % 3] : 0.f;
 }
 
-// rot @ v per component as validate forms it: (v0 * rot[k][0] + v1 * rot[k][1]) + v2 * rot[k][2]
-__device__ __forceinline__ float rot_row(const float* __restrict__ rot, int k, float v0, float v1, float v2) {
-    return (v0 * rot[3 * k] + v1 * rot[3 * k + 1]) + v2 * rot[3 * k + 2];
-}
-
 __global__ __launch_bounds__(256) void surface_pack_k(gens_surface_pack_args a) {
     const int j = (int)(blockIdx.x * 256u + threadIdx.x);
     if (j >= (int)a.m) return;
@@ -174,7 +169,7 @@ __global__ __launch_bounds__(256) void surface_pack_k(gens_surface_pack_args a) 
     const int r = (int)r64;
     const bool hit = a.status[r] == T_HIT;
     if (a.hit) a.hit[r] = hit ? 1 : 0;
-    if (a.depth) a.depth[r] = hit ? a.t[r] * rot_row(a.rot, 2, a.rays_d[3 * r], a.rays_d[3 * r + 1], a.rays_d[3 * r + 2]) : 0.f;
+    if (a.depth) a.depth[r] = hit ? gens_pack_depth(a.rot, a.t[r], a.rays_d[3 * r], a.rays_d[3 * r + 1], a.rays_d[3 * r + 2]) : 0.f;
     if (a.grad) {
         float nx = 0.f, ny = 0.f, nz = 0.f;
         if (hit) gens_unit_normal(a.grad[3 * j], a.grad[3 * j + 1], a.grad[3 * j + 2], nx, ny, nz);
@@ -185,7 +180,7 @@ __global__ __launch_bounds__(256) void surface_pack_k(gens_surface_pack_args a) 
         }
         if (a.normal_img) {
             for (int k = 0; k < 3; ++k)
-                a.normal_img[3 * r + k] = hit ? fminf(fmaxf(rot_row(a.rot, k, nx, ny, nz) * 128.f + 128.f, 0.f), 255.f) : 0.f;
+                a.normal_img[3 * r + k] = hit ? gens_normal_img(a.rot, k, nx, ny, nz) : 0.f;
         }
     }
     if (a.color) {

@@ -15,13 +15,11 @@
 // every operation rounded on its own (no contraction), results rounded once to float32.
 #include <math.h>
 
+#include "atlas_rules.h"
 #include "common.h"
 #include "pack_rules.h"
 
 #pragma clang fp contract(off)
-
-#define K34_MIN_TEXELS 3
-#define K34_MAX_TEXELS 64
 
 // Sample number k of a triangle -> its local texel (i', j'): j' is the outer index, row j' holds S - j' texels and begins at
 // j' S - j' (j' - 1) / 2.  The float estimate is corrected in integers, so the result is exact.
@@ -33,15 +31,6 @@ __device__ __forceinline__ void k34_local(int S, int k, int& ip, int& jp) {
     while (j < S - 1 && (j + 1) * S - (j + 1) * j / 2 <= k) ++j;
     ip = k - (j * S - j * (j - 1) / 2);
     jp = j;
-}
-
-// Local texel (i', j') of triangle f -> its pixel (x, y): tile f >> 1 at column q % cols and row q / cols, half f & 1 turned by a half turn.
-__device__ __forceinline__ void k34_pixel(int S, int cols, int64_t f, int ip, int jp, int64_t& x, int64_t& y) {
-    const int64_t q = f >> 1;
-    const bool turned = (f & 1) != 0;
-    const int i = turned ? S - ip : ip, j = turned ? S - 1 - jp : jp;
-    x = (q % cols) * (S + 1) + i;
-    y = (q / cols) * S + j;
 }
 
 __device__ __forceinline__ double k34_edge2(double ax, double ay, double az, double bx, double by, double bz) {
@@ -150,16 +139,6 @@ __global__ __launch_bounds__(256) void texture_uv_k(int64_t n_faces, int S, int 
 
 // ------------------------------------------------------------------------------------------------ entry points
 #define K34_LIMIT ((int64_t)1 << 31)
-
-// The atlas of n_faces triangles: cols = ceil(sqrt(n_tiles)) in exact integers, rows = ceil(n_tiles / cols).
-static void k34_layout(int64_t n_faces, int texels, int64_t& cols, int64_t& rows) {
-    const int64_t tiles = (n_faces + 1) / 2;
-    int64_t c = (int64_t)sqrt((double)tiles);
-    while (c * c < tiles) ++c;
-    while (c > 0 && (c - 1) * (c - 1) >= tiles) --c;
-    cols = c;
-    rows = c ? (tiles + c - 1) / c : 0;
-}
 
 #define K34_CHECK_SHAPE(who)                                                                                                                         \
     GENS_CHECK_ARG(texels >= K34_MIN_TEXELS && texels <= K34_MAX_TEXELS, GENS_EINVAL, who ": texels = %d (%d to %d)", texels, K34_MIN_TEXELS,         \

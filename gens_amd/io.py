@@ -406,6 +406,8 @@ def save_validation_outputs(base_exp_dir, outputs, inputs, tag, image_tag=None, 
     outputs["surface_depth"] / ["surface_normal_img"] / ["surface_img"] (validate's surface_render), where present, are written under
     val_surface_depth/, val_surface_normal/ and val_surface_img/ by the writers of their volume-rendered counterparts; pixels whose ray did
     not hit the surface are black.
+    outputs["mesh_depth"] / ["mesh_normal_img"] / ["mesh_img"] (validate's mesh_render, K35), where present, are written in the same way
+    under val_mesh_depth/, val_mesh_normal/ and val_mesh_img/; pixels whose ray did not hit the mesh (outputs["mesh_hit"]) are black.
     outputs["fused_points"] (validate's surface_fusion), where present, is written as pcd/{scene}_{tag}.ply (write_point_cloud) in world
     coordinates (transform_vertices / transform_normals with scale_mat), with fused_normals and fused_colors where present; colours of points
     no source view sees (fused_seen False) are written mid-grey.  Copied to pcd/scan{n}.ply it is what evaluate_dtu(mode="pcd") reads.
@@ -451,14 +453,16 @@ def save_validation_outputs(base_exp_dir, outputs, inputs, tag, image_tag=None, 
     paths["sdf_depth"] = os.path.join(base_exp_dir, "val_sdf_depth", f"{image_tag}_{tag}.png")
     save_depth(outputs["sdf_depth"], paths["sdf_depth"])
     for key, sub, name in (("surface_depth", "val_surface_depth", "surface_depth"), ("surface_normal_img", "val_surface_normal", "surface_normal"),
-                           ("surface_img", "val_surface_img", "surface_img")):
+                           ("surface_img", "val_surface_img", "surface_img"), ("mesh_depth", "val_mesh_depth", "mesh_depth"),
+                           ("mesh_normal_img", "val_mesh_normal", "mesh_normal"), ("mesh_img", "val_mesh_img", "mesh_img")):
         if key not in outputs:
             continue
         os.makedirs(os.path.join(base_exp_dir, sub), exist_ok=True)
         paths[name] = os.path.join(base_exp_dir, sub, f"{image_tag}_{tag}.png")
-        rgb = depth_to_rgb(outputs[key]) if key == "surface_depth" else np.asarray(outputs[key]).astype(np.uint8)
-        if outputs.get("surface_hit") is not None:        # (the colour map's lowest entry is not quite black)
-            rgb = np.where(np.asarray(outputs["surface_hit"], dtype=bool)[:, :, None], rgb, np.uint8(0))
+        rgb = depth_to_rgb(outputs[key]) if key.endswith("_depth") else np.asarray(outputs[key]).astype(np.uint8)
+        hit = outputs.get(key.split("_")[0] + "_hit")
+        if hit is not None:                               # (the colour map's lowest entry is not quite black)
+            rgb = np.where(np.asarray(hit, dtype=bool)[:, :, None], rgb, np.uint8(0))
         Image.fromarray(rgb).save(paths[name])
     if "fused_points" in outputs:
         os.makedirs(os.path.join(base_exp_dir, "pcd"), exist_ok=True)

@@ -74,6 +74,13 @@ class ClusterSolveArgs(C.Structure):  # gens_cluster_solve_args (K33)
         (n, _p) for n in ("out_vertices", "source", "fell_back")]
 
 
+class MeshShadeArgs(C.Structure):     # gens_mesh_shade_args (K35)
+    _fields_ = [("vertices", _p), ("triangles", _p), ("n_vertices", _l), ("n_faces", _l), ("rays_o", _p), ("rays_d", _p), ("face", _p), ("t", _p),
+                ("n", _l)] + [(n, _p) for n in ("rot", "vertex_normals", "vertex_colors", "vertex_seen", "atlas", "atlas_seen")] + [
+        ("atlas_h", _l), ("atlas_w", _l), ("texels", _i), ("shading", _i), ("orient", _i)] + [
+        (n, _p) for n in ("hit", "bary", "depth", "normal", "normal_img", "img", "seen")]
+
+
 # name -> argtypes, mirroring include/gens_hip.h declaration by declaration
 SIGNATURES = {
     "gens_pack_nchw": [_p, _p, _i, _i, _i, _i, _p],
@@ -241,6 +248,7 @@ SIGNATURES = {
     "gens_texture_keep_better": [_p, _p, _p, _p, _p, _p, _f, _l, _p, _p],
     "gens_texture_pack": [_p, _p, _i, _l, _i, _l, _l, _p, _p, _p],
     "gens_texture_uv": [_l, _i, _p, _p],
+    "gens_mesh_shade": [C.POINTER(MeshShadeArgs), _p],
 }
 
 _lib = None

@@ -112,6 +112,9 @@ class GenS(nn.Module):
         texture = confs.get("mesh_texture", None)               # optional: extract_geometry / validate also return a texture atlas of the mesh (texture_mesh, K34); the tile edge in texels or its keywords
         if texture is not None:
             self.implicit_surface.mesh_texture = dict(texture) if hasattr(texture, "keys") else texture
+        mesh_render = confs.get("mesh_render", None)            # optional: validate also casts its rays at the extracted mesh (render_mesh, K35); True or its keywords
+        if mesh_render is not None:
+            self.implicit_surface.mesh_render = dict(mesh_render) if hasattr(mesh_render, "keys") else bool(mesh_render)
         lipschitz = confs.get("lattice_lipschitz", None)        # optional: the bound that lattice assumes (ImplicitSurface.lattice_lipschitz)
         if lipschitz is not None:
             self.implicit_surface.lattice_lipschitz = float(lipschitz)

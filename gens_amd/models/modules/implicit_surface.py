@@ -1019,6 +1019,92 @@ class ImplicitSurface(nn.Module):
             del out["depth"]
         return out
 
+    mesh_render = None             # validate also casts its rays at the mesh it extracted (render_mesh, K35) and returns mesh_depth, mesh_normal_img,
+                                   # mesh_img and mesh_hit (and mesh_fidelity beside surface_render).  None / False: off; True: on; or a dict of
+                                   # render_mesh's keywords (shading, chunk)
+    last_mesh_render_stats = None  # rays, hits, grid cells and faces of the last render_mesh call
+    _MESH_RENDER_KEYS = ("shading", "chunk")
+
+    def _mesh_render_option(self, mesh_render):
+        """The mesh render validate asks for (None: the attribute `mesh_render`) -> a dict of render_mesh's keywords, or None for off."""
+        mesh_render = self.mesh_render if mesh_render is None else mesh_render
+        if mesh_render is None or mesh_render is False:
+            return None
+        if mesh_render is True:
+            return {}
+        if not isinstance(mesh_render, dict):
+            raise ValueError(f"mesh_render = {mesh_render!r}: None / False, True, or a dict of {self._MESH_RENDER_KEYS!r}")
+        unknown = [k for k in mesh_render if k not in self._MESH_RENDER_KEYS]
+        if unknown:
+            raise ValueError(f"mesh_render: unknown keywords {unknown!r}: the known ones are {self._MESH_RENDER_KEYS!r}")
+        if mesh_render.get("shading", "flat") not in ops.MESH_SHADINGS:
+            raise ValueError(f"mesh_render: shading = {mesh_render['shading']!r}: one of {ops.MESH_SHADINGS!r}")
+        return dict(mesh_render)
+
+    @torch.no_grad()
+    def render_mesh(self, points, triangles, rays_o, rays_d, c2ws, normals=None, colors=None, seen=None, texture=None, texture_seen=None,
+                    texels=None, shading="flat", hw=None, chunk=None):
+        """A triangle mesh in the model's frame as the rays see it (K35): the counterpart of render_surface for the
+        asset that is written to disk.  points (V, 3) and triangles (T, 3), rays_o / rays_d (n, 3) or (H, W, 3), c2ws: numpy arrays or
+        tensors, from anywhere -- an extracted, simplified, cleaned or read mesh; everything is moved to the device of this module's
+        parameters (rays and poses that are device tensors already decide it).  It needs no volumes and no network.
+        normals (V, 3), colors (V, 3) uint8, seen (V): vertex_attributes' dict; texture (H, W, 3) uint8, texture_seen, texels:
+        texture_mesh's atlas of this very mesh and the tile edge it was made with (default: read off the atlas' shape) -- the atlas is used
+        where given, else the vertex colours, else only depth and normals are produced.  shading "flat" (the face's normal) or "smooth"
+        (the vertex normals interpolated; needs `normals`).  rot = inverse(c2ws[0][:3,:3]), as validate and render_surface form it.
+        -> dict of host arrays shaped (H, W, ...) by hw or the rays' own leading shape, else flat: "face" int32 (-1: miss), "t" float32
+        (+inf: miss), "hit" bool, "bary" (.., 3), "depth" = t (rot d)_z, "normal" (.., 3), "normal_img" (.., 3) float32 in validate's
+        convention, and with colours "img" (.., 3) uint8, with their flags "seen" bool.  Everything is 0 where the ray misses the mesh.
+        One sample per ray: no anti-aliasing, mip-maps or lighting.  self.last_mesh_render_stats: "rays", "hits", "cells", "faces"."""
+        shape = tuple(int(v) for v in hw) if hw is not None else tuple(rays_o.shape[:-1])
+        out = self._render_mesh(points, triangles, rays_o, rays_d, c2ws, normals, colors, seen, texture, texture_seen, texels, shading, chunk)
+        out["hit"] = out["hit"].bool()
+        if "seen" in out:
+            out["seen"] = out["seen"].bool()
+        return {k: v.cpu().numpy().reshape(shape + tuple(v.shape[1:])) for k, v in out.items()}
+
+    @torch.no_grad()
+    def _render_mesh(self, points, triangles, rays_o, rays_d, c2ws, normals, colors, seen, texture, texture_seen, texels, shading, chunk):
+        """render_mesh on the device: its arguments -> ops.render_mesh's dict of flat per-ray device tensors."""
+        dev = next((t.device for t in (rays_o, rays_d, c2ws, points) if torch.is_tensor(t) and t.is_cuda), None)
+        if dev is None:
+            dev = next(self.parameters()).device
+        tri = torch.as_tensor(triangles)
+        if tri.dim() != 2 or tri.shape[1] != 3:
+            raise ValueError(f"render_mesh: triangles are {tuple(tri.shape)}, expected (T, 3)")
+        if shading not in ops.MESH_SHADINGS:
+            raise ValueError(f"render_mesh: shading = {shading!r}: one of {ops.MESH_SHADINGS!r}")
+        if shading == "smooth" and normals is None:
+            raise ValueError("render_mesh: smooth shading needs the vertex normals")
+        if seen is not None and colors is None:
+            raise ValueError("render_mesh: seen flags come with the vertex colours")
+        if texture_seen is not None and texture is None:
+            raise ValueError("render_mesh: texture_seen without a texture")
+        n_faces = int(tri.shape[0])
+        if texture is not None:
+            tex_shape = tuple(texture.shape)
+            if texels is None:
+                texels = ops.atlas_texels(n_faces, tex_shape)
+            if ops.texture_layout(n_faces, texels)[:2] + (3,) != tex_shape:
+                raise ValueError(f"render_mesh: a texture of {tex_shape} for {n_faces} triangles with texels = {texels}: expected "
+                                 f"{ops.texture_layout(n_faces, texels)[:2] + (3,)}")
+        if not torch.is_tensor(c2ws) and np.asarray(c2ws).shape[-2:] != (4, 4):
+            raise ValueError(f"render_mesh: c2ws are {np.asarray(c2ws).shape}, expected (nv, 4, 4)")
+        up = lambda v, dtype, cols: None if v is None else torch.as_tensor(v).detach().to(device=dev).reshape((-1,) + cols).to(dtype).contiguous()  # noqa: E731
+        f32, u8 = torch.float32, torch.uint8
+        c2ws = up(c2ws, f32, (4, 4))
+        o, d = up(rays_o, f32, (3,)), up(rays_d, f32, (3,))
+        grid = ops.build_mesh_grid(up(points, torch.float64, (3,)), up(tri, torch.int32, (3,)))
+        rot = ops.SceneCams(torch.eye(4, device=dev).expand(c2ws.shape[0], 4, 4).contiguous(), c2ws).rot_inv
+        if texture is not None:
+            texture = torch.as_tensor(texture).detach().to(device=dev, dtype=u8).contiguous()
+            texture_seen = None if texture_seen is None else torch.as_tensor(texture_seen).detach().to(device=dev).to(u8).contiguous()
+        out = ops.render_mesh(None, None, o, d, rot, grid=grid, chunk=chunk, normals=up(normals, f32, (3,)), colors=up(colors, u8, (3,)),
+                              seen=up(seen, u8, ()), texture=texture, texture_seen=texture_seen, texels=texels, shading=shading)
+        self.last_mesh_render_stats = {"rays": int(o.shape[0]), "hits": int(out["hit"].sum()), "faces": n_faces,
+                                       "cells": grid.dims[0] * grid.dims[1] * grid.dims[2]}
+        return out
+
     surface_fusion = None          # validate also fuses the sphere-traced depth maps of the item's views into a point cloud (fuse_surface, K32) and
                                    # returns fused_points, fused_normals, fused_colors and fused_seen.  None / False: off; True: on; or a dict of
                                    # fuse_surface's keywords (pairs, pix_tol, rel_tol, min_views, normal_cos, dedupe_radius, and render_surface's)
@@ -1185,7 +1271,8 @@ class ImplicitSurface(nn.Module):
     @torch.no_grad()
     def validate(self, rays_o, rays_d, near, far, volumes, mask_volumes, imgs, features, match_features, intrs, c2ws, bound_min, bound_max,
                  hw, cos_anneal_ratio=1.0, step=None, extract_geometry=True, mesh_resolution=512, threshold=0.0, scene=None, shard=None, sparse=None,
-                 sparse_mesh=None, mesh_attributes=None, surface_render=None, surface_fusion=None, mesh_simplify=None, mesh_texture=None):
+                 sparse_mesh=None, mesh_attributes=None, surface_render=None, surface_fusion=None, mesh_simplify=None, mesh_texture=None,
+                 mesh_render=None):
         """shard (gens_amd.distributed.Shard, optional): render only this rank's contiguous ray range and evaluate only its lattice
         chunks; the (P, 8) image buffer / the lattice slabs are gathered over RCCL, so every rank returns the whole image.  The jitter
         of EVERY ray is drawn on every rank from the identically seeded CPU generator (the reference's draw order) and sliced with
@@ -1201,8 +1288,21 @@ class ImplicitSurface(nn.Module):
         attributes are those of the simplified mesh (K33); self.last_simplify_stats holds its counts.  mesh_texture: extract_geometry's
         `texture` with this scene's views (the tile edge in texels or a dict of texture_mesh's keywords; default: the attribute of that name,
         None / False / 0 = off) -> outputs["texture"], ["texture_seen"], ["texture_uv"] (K34), which save_validation_outputs writes as an
-        OBJ beside the PLY."""
+        OBJ beside the PLY.  mesh_render (default: the attribute of that name, None / False = off; True, or a dict of render_mesh's keywords
+        shading and chunk): after extract_geometry the rays of this image are cast at the mesh it returned (render_mesh, K35), with the
+        atlas where that call made one, else the vertex colours where it made them, else neither -> outputs["mesh_depth"],
+        ["mesh_normal_img"], ["mesh_hit"] and, with colours, ["mesh_img"]; beside surface_render also outputs["mesh_fidelity"] =
+        ops.compare_maps(mesh maps, surface maps).  ValueError before any launch with a shard, with extract_geometry=False, or for
+        smooth shading when mesh_attributes does not ask for "normals"."""
         outputs = {}
+        mesh_render = self._mesh_render_option(mesh_render)
+        if mesh_render is not None and (shard is not None or not extract_geometry):
+            raise ValueError("mesh_render casts the rays at the mesh of this call on one rank: not with a shard, not with extract_geometry=False "
+                             "(render_mesh takes any mesh)")
+        if mesh_render is not None and mesh_render.get("shading") == "smooth":
+            asked = self.mesh_attributes if mesh_attributes is None else mesh_attributes
+            if "normals" not in ((asked,) if isinstance(asked, str) else tuple(asked or ())):
+                raise ValueError("mesh_render: smooth shading needs mesh_attributes with \"normals\"")
         mesh_simplify = self._simplify_request(mesh_simplify) if extract_geometry else None      # (refused before anything is launched)
         mesh_texture = self._texture_option(mesh_texture) if extract_geometry else None
         surface_fusion = self.surface_fusion if surface_fusion is None else surface_fusion
@@ -1310,6 +1410,16 @@ class ImplicitSurface(nn.Module):
                                        threshold=threshold, hw=(height, width), **surface_kw)
             outputs["surface_depth"], outputs["surface_normal_img"] = surf["depth"], surf["normal_img"]
             outputs["surface_img"], outputs["surface_hit"] = surf["img"], surf["hit"]
+        if mesh_render is not None:
+            maps = self.render_mesh(outputs["vertices"], outputs["triangles"], rays_o, rays_d, c2ws, normals=outputs.get("vertex_normals"),
+                                    colors=outputs.get("vertex_colors"), seen=outputs.get("vertex_seen") if "vertex_colors" in outputs else None,
+                                    texture=outputs.get("texture"), texture_seen=outputs.get("texture_seen"),
+                                    texels=None if mesh_texture is None else mesh_texture.get("texels", 8), hw=(height, width), **mesh_render)
+            outputs["mesh_depth"], outputs["mesh_normal_img"], outputs["mesh_hit"] = maps["depth"], maps["normal_img"], maps["hit"]
+            if "img" in maps:
+                outputs["mesh_img"] = maps["img"]
+            if surface_render:
+                outputs["mesh_fidelity"] = ops.compare_maps(maps, surf)
         if surface_fusion:
             cloud = self.fuse_surface(scene.volumes_nograd(), intrs, c2ws, (height, width), bound_min, bound_max, views=scene.views,
                                       **{"threshold": threshold, **fusion_kw})

@@ -29,6 +29,7 @@ is what it was when ops was one module:
     ops.fusion    K32: per-view depth maps fused into a consistency-filtered point cloud (fusion_cams, fuse_depth_maps, fused_points).
     ops.simplify  K33: mesh simplification by vertex clustering with quadric-optimal representatives (simplify_mesh).
     ops.texture   K34: texture atlases for triangle meshes: atlas samples to points, the guarded Newton snap, colours to pixels, corner coordinates.
+    ops.mesh_render  K35: a mesh as rays see it: shading at K23's first hits (shade_mesh_hits), grid -> first hit -> shade (render_mesh), compare_maps.
 """
 from .base import *  # noqa: F401,F403
 from .volume import *  # noqa: F401,F403
@@ -50,3 +51,4 @@ from .trace import *  # noqa: F401,F403
 from .fusion import *  # noqa: F401,F403
 from .simplify import *  # noqa: F401,F403
 from .texture import *  # noqa: F401,F403
+from .mesh_render import *  # noqa: F401,F403

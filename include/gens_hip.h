@@ -66,7 +66,7 @@ const char* gens_last_error(void);
  *       and K30's gens_vertex_points, gens_vertex_pack, and K31's gens_trace_begin, gens_trace_march, gens_trace_refine, gens_trace_gather,
  *       gens_surface_pack, and K32's gens_fuse_depth_maps, gens_fused_points, and K33's gens_cluster_keys, gens_cluster_triangles,
  *       gens_cluster_solve, and K34's gens_texture_points, gens_texture_snap, gens_texture_keep_better,
- *       gens_texture_pack, gens_texture_uv. */
+ *       gens_texture_pack, gens_texture_uv, and K35's gens_mesh_shade. */
 int gens_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -1178,6 +1178,78 @@ int gens_texture_keep_better(float* points, float* value, float* grad, const flo
 int gens_texture_pack(const float* color, const uint8_t* vis, int n_src, int64_t n_faces, int texels, int64_t s0, int64_t s1, uint8_t* atlas,
                       uint8_t* seen, void* stream);
 int gens_texture_uv(int64_t n_faces, int texels, float* uv, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * K35  Depth, normal and colour maps of a triangle mesh at the first hits of rays (ops.shade_mesh_hits / render_mesh,
+ *      ImplicitSurface.render_mesh, validate(mesh_render=)), csrc/k35_mesh_shade.hip: the shading behind K23's gens_ray_first_hit.
+ *      tests/mesh_render_reference.py restates all of it in numpy.
+ *
+ *   Definition.  Arithmetic is float64 from the stored inputs (float64 vertices, float32 rays, t, vertex normals; bytes), every operation
+ *   rounded on its own, in the order written; results are rounded once.  dot(u, v) = (u_x v_x + u_y v_y) + u_z v_z.  A, B, C are the
+ *   corners of the ray's face in stored order.
+ *     1. Hit.  A ray is a hit iff 0 <= face < T, t is finite and > 0, the face's three indices lie in 0 .. V - 1 and the nine coordinates
+ *        of its corners are finite (gens_ray_first_hit never returns such a face; planted input may name one).  A face or vertex index
+ *        outside its range is never read through.  Every output of a ray that is not a hit is 0.
+ *     2. Depth = t (rot d)_z in float32: K31's pack rule, the same device function (csrc/pack_rules.h), so the mesh map and the surface
+ *        map of one ray differ only through t.
+ *     3. Barycentrics.  p = o + t d per component;  e1 = B - A,  e2 = C - A,  w = p - A;  d11 = dot(e1, e1),  d12 = dot(e1, e2),
+ *        d22 = dot(e2, e2),  w1 = dot(w, e1),  w2 = dot(w, e2);  den = d11 d22 - d12 d12;  b = (d22 w1 - d12 w2) / den,
+ *        c = (d11 w2 - d12 w1) / den.  If den > 0 is false (a NaN included), or b or c is not finite: (a, b, c) = (1, 0, 0).  Otherwise
+ *        b and c that are not > 0 become 0;  s = b + c;  if s > 1: b = b / s, c = c / s;  a = (1 - b) - c, and an a that is not > 0
+ *        becomes 0.  This is the least-squares foot of p in the face's plane, clamped into the face: the hit point of a watertight float64
+ *        test lies in the face up to rounding, so the clamp removes that rounding only.  0 <= a, b, c <= 1 always.  bary = (a, b, c)
+ *        rounded to float32; everything below uses the float64 values.
+ *     4. Normal.  Flat: n = e1 x e2 = (e1_y e2_z - e1_z e2_y,  e1_z e2_x - e1_x e2_z,  e1_x e2_y - e1_y e2_x), each component negated if
+ *        orient = 1.  Smooth: n = (a n_A + b n_B) + c n_C per component, from vertex_normals; orient does not enter.  normal = K30's unit
+ *        normal of n (csrc/pack_rules.h): n / sqrt((n_x^2 + n_y^2) + n_z^2), rounded once; (0, 0, 0) where a component is not finite or
+ *        the norm is 0.  normal_img = K31's, from the float32 normal: min(max((rot normal) 128 + 128, 0), 255) in float32.
+ *        gens_mc_emit and gens_brick_mc_emit wind their triangles so that e1 x e2 points along + grad sdf (out of the object, towards the
+ *        side K12 calls u < iso): orient = 0 is the default of every caller, orient = 1 is for meshes wound the other way.
+ *     5. Colour from vertices (no atlas).  Per channel x = (a c_A + b c_B) + c c_C on the uint8 values; img = floor(x + 0.5) clamped to
+ *        0 .. 255.  seen = 1 iff every corner whose weight is > 0 has vertex_seen != 0.
+ *     6. Colour from the atlas (K34's layout, texels = S).  x = b (S - 2),  y = c (S - 2);  i0 = floor(x),  j0 = floor(y);  fx = x - i0,
+ *        fy = y - j0.  The taps are the local texels (i0, j0), (i0 + 1, j0), (i0, j0 + 1), (i0 + 1, j0 + 1) with the weights
+ *        (1 - fx)(1 - fy),  fx (1 - fy),  (1 - fx) fy,  fx fy.  A tap whose weight is not > 0 is not read and its term is 0; another
+ *        tap's term is weight times the byte at K34's pixel of that local texel of the face (tile face >> 1, half face & 1).  Per channel
+ *        x = ((term00 + term10) + term01) + term11; img as in 5.  seen = 1 iff every tap with a weight > 0 has atlas_seen != 0.
+ *        Since 0 <= b, c <= 1, every tap read has 0 <= i', j' <= S - 1: a texel of the face's own tile.  Up to the roundings of step 3
+ *        it also has i' + j' <= S - 1, a texel of the face itself: the rule does not cross the seams between tile halves.  At the
+ *        corners A, B, C the colour is that of the local texels (0, 0), (S - 2, 0), (0, S - 2), bit for bit.
+ *   NOT promised: anti-aliasing, mip-maps, lighting, a rasteriser.  One sample per ray.
+ *
+ *   gens_mesh_shade: one thread per ray.  vertices (V, 3) float64, triangles (T, 3) int32 (what gens_mesh_grid holds); rays_o, rays_d
+ *     (n, 3) float32; face (n) int32 and t (n) float32 as gens_ray_first_hit wrote them; rot: 9 floats (K31's).  Optional (NULL: absent):
+ *     vertex_normals (V, 3) float32, vertex_colors (V, 3) uint8, vertex_seen (V) uint8; atlas (atlas_h, atlas_w, 3) uint8, atlas_seen
+ *     (atlas_h, atlas_w) uint8 with texels = S.  With an atlas, colour and seen come from it and the vertex colours are not read.
+ *     shading: 0 flat, 1 smooth; orient: 0 as wound, 1 reversed.  Outputs, any of which may be NULL (not written, and what only it needs
+ *     is not read): hit (n) uint8, bary (n, 3) float32, depth (n) float32, normal (n, 3) float32, normal_img (n, 3) float32, img (n, 3)
+ *     uint8, seen (n) uint8.  All pointers are device pointers.
+ *   Arguments are checked before any launch.  GENS_EINVAL: a null argument block; negative n, V or T; shading or orient outside 0 .. 1;
+ *     with an atlas, texels outside 3 .. 64 or atlas_h, atlas_w that are not K34's layout of T and S; atlas_seen without an atlas; smooth
+ *     shading without vertex_normals; img or seen requested with neither vertex_colors nor an atlas; seen requested without the seen
+ *     plane of the colour's source; with n > 0 and some output requested, a null pointer the launch would dereference (face, t,
+ *     triangles with T > 0, vertices with V > 0, rays_d, rays_o and rot where a requested output needs them).  GENS_ELIMIT: n, V or
+ *     T >= 2^31.  n == 0, and no output requested, succeed without a launch.  The ABI version stays 12: no existing entry changes.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    const double* vertices;
+    const int32_t* triangles;
+    int64_t n_vertices, n_faces;
+    const float *rays_o, *rays_d;
+    const int32_t* face;
+    const float* t;
+    int64_t n;
+    const float* rot;
+    const float* vertex_normals;
+    const uint8_t *vertex_colors, *vertex_seen;
+    const uint8_t *atlas, *atlas_seen;
+    int64_t atlas_h, atlas_w;
+    int texels, shading, orient;
+    uint8_t* hit;
+    float *bary, *depth, *normal, *normal_img;
+    uint8_t *img, *seen;
+} gens_mesh_shade_args;
+int gens_mesh_shade(const gens_mesh_shade_args* args, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K14  C (m x n) = A^T B for tall row-major operands A (k x m), B (k x n), k >> m, n: the weight-gradient product of the training
