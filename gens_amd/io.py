@@ -370,6 +370,35 @@ def simplify_mesh(vertices, triangles, cell, origin=None, normals=None, colors=N
     return out_v.cpu().numpy(), out_t.cpu().numpy().astype(t_int.dtype if np.issubdtype(t_int.dtype, np.integer) else np.int32), attrs
 
 
+@torch.no_grad()
+def compare_meshes(va, ta, vb, tb, device=None, **kw):
+    """ops.mesh_distance (K36: exact point-to-triangle distances, both ways) for host meshes, numpy in like the cleaners: vertices (V,3),
+    triangles (F,3) of the meshes A and B (arrays or tensors); kw: ops.mesh_distance's density, samples, max_dist -> its dict as plain Python
+    numbers (a_to_b / b_to_a with n, unmatched, mean, rms, max, q50, q90, q99; hausdorff; chamfer; density_a, density_b).  ValueError for what
+    ops.mesh_distance refuses, for triangle indices outside the vertices and for vertices that are not finite, before the device is
+    looked at."""
+    from . import ops
+    unknown = sorted(set(kw) - set(ops.MESH_DISTANCE_KEYS))
+    if unknown:
+        raise ValueError(f"compare_meshes: unknown keyword {unknown[0]!r} (ops.mesh_distance's {', '.join(ops.MESH_DISTANCE_KEYS)})")
+    ops.mesh_distance_request("compare_meshes", **kw)
+    meshes = []
+    for name, v, t in (("A", va, ta), ("B", vb, tb)):
+        v_np = np.ascontiguousarray(as_numpy(v), dtype=np.float64).reshape(-1, 3)
+        t_np = np.asarray(as_numpy(t)).reshape(-1, 3)
+        if t_np.size and (t_np.min() < 0 or t_np.max() >= len(v_np)):
+            raise ValueError(f"compare_meshes: mesh {name}: triangle indices {t_np.min()} .. {t_np.max()} outside the {len(v_np)} vertices")
+        if not np.isfinite(v_np).all():
+            raise ValueError(f"compare_meshes: mesh {name}: a vertex is not finite")
+        meshes.append((v_np, np.ascontiguousarray(t_np, dtype=np.int32)))
+    dev = device_of(va, ta, vb, tb, device=device)
+    out = ops.mesh_distance(*[torch.from_numpy(x).to(dev) for mesh in meshes for x in mesh], **kw)
+
+    def plain(x):
+        return {k: plain(v) for k, v in x.items()} if isinstance(x, dict) else (int(x) if isinstance(x, (int, np.integer)) else float(x))
+    return plain(out)
+
+
 def dilate_masks(masks, radius=11):
     """utils/clean_mesh.py:119-125: masks (nv,H,W[,3]) > 0.5, dilated by a disk of `radius` pixels (skimage.morphology.disk)."""
     from scipy import ndimage

@@ -249,6 +249,7 @@ SIGNATURES = {
     "gens_texture_pack": [_p, _p, _i, _l, _i, _l, _l, _p, _p, _p],
     "gens_texture_uv": [_l, _i, _p, _p],
     "gens_mesh_shade": [C.POINTER(MeshShadeArgs), _p],
+    "gens_mesh_closest_point": [C.POINTER(MeshGridArgs), _p, _l, _d, _p, _p, _p, _p, _p],
 }
 
 _lib = None

@@ -594,6 +594,28 @@ class ImplicitSurface(nn.Module):
             raise ValueError("simplify = True: pass the cell edge in lattice spacings (a positive number; None, False or 0: off)")
         return ops.simplify_request("simplify", simplify)[0]
 
+    mesh_simplify_error = None     # True or a dict of ops.mesh_distance's keywords (density, samples, max_dist): extract_geometry / validate measure the
+                                   # simplified mesh against the mesh it came from (K36) -> last_simplify_stats["error"].  None / False: off
+
+    def _simplify_error_request(self, simplify_error, simplify):
+        """The error measurement a mesh call asks for (None: the attribute `mesh_simplify_error`) beside its checked `simplify` -> a dict of
+        ops.mesh_distance's keywords, or None for none.  ValueError for anything but None, a bool or such a dict, and when it is asked for
+        with the simplification off."""
+        simplify_error = self.mesh_simplify_error if simplify_error is None else simplify_error
+        if simplify_error is None or simplify_error is False:
+            return None
+        if simplify_error is True:
+            simplify_error = {}
+        if not isinstance(simplify_error, dict):
+            raise ValueError(f"simplify_error = {simplify_error!r}: True, or a dict of ops.mesh_distance's keywords (None or False: off)")
+        unknown = sorted(set(simplify_error) - set(ops.MESH_DISTANCE_KEYS), key=str)
+        if unknown:
+            raise ValueError(f"simplify_error: unknown keyword {unknown[0]!r} (ops.mesh_distance's {', '.join(ops.MESH_DISTANCE_KEYS)})")
+        ops.mesh_distance_request("simplify_error", **simplify_error)
+        if simplify is None:
+            raise ValueError("simplify_error measures the simplified mesh against the extracted one: it needs simplify (a cell edge in lattice spacings)")
+        return dict(simplify_error)
+
     mesh_texture = None            # the tile edge in texels (3 to 64), or a dict of texture_mesh's keywords (texels, snap, max_move, chunk):
                                    # extract_geometry / validate also return a texture atlas of the mesh (texture_mesh, K34).  None / False / 0:
                                    # off (DESIGN.md, section 5k)
@@ -1206,7 +1228,7 @@ class ImplicitSurface(nn.Module):
         return out
 
     def extract_geometry(self, volumes, bound_min, bound_max, resolution, threshold, shard=None, sparse=None, sparse_mesh=None, attributes=None,
-                         views=None, simplify=None, texture=None):
+                         views=None, simplify=None, texture=None, simplify_error=None):
         """-> vertices (V,3) float64, triangles (T,3) int32 as numpy arrays (implicit_surface.py:407-427).  The SDF lattice and
         the marching cubes both run on the device (the reference: 512 D2H copies + PyMCubes on the host); only the mesh is copied.
         sparse: sdf_grid's option of that name, with this call's threshold.  sparse_mesh (default: the attribute of that name, None = off):
@@ -1224,6 +1246,12 @@ class ImplicitSurface(nn.Module):
         on every rank that holds the gathered mesh.  self.last_simplify_stats: its counts (None when off).  Topology is not preserved and no
         distance to the surface is promised.  ValueError before any launch for a cell edge that is not a positive
         finite number.
+        simplify_error (default: the attribute `mesh_simplify_error`; None or False = off): True, or a dict of ops.mesh_distance's keywords
+        (density, samples, max_dist).  The device-resident mesh from before the simplification is kept until after it and the two are
+        compared in index coordinates (ops.mesh_distance with A = the extracted mesh, B = the simplified one; K36): the dict goes into
+        self.last_simplify_stats["error"], in lattice spacings -- b_to_a.max bounds how far a simplified vertex is from the extracted surface,
+        a_to_b what of that surface the simplified mesh lost.  Off: nothing is kept or launched and the stats have no such key.  ValueError
+        before any launch for another value, unknown or bad keywords, or when simplify is off.
         texture (default: the attribute `mesh_texture`; None, False or 0 = off): the tile edge in texels (3 to 64) or a dict of texture_mesh's
         keywords (texels, snap, max_move, chunk) -> a further result after the attribute dict (whose place holds None when only the
         texture is asked for): texture_mesh's dict for the returned mesh (K34), computed after marching cubes and
@@ -1232,6 +1260,7 @@ class ImplicitSurface(nn.Module):
         refuses; the atlas edge (at most 16 384 pixels) can only be checked once the mesh exists, before any texture launch."""
         attributes = self._attribute_request(attributes, volumes, views)
         simplify = self._simplify_request(simplify)
+        simplify_error = self._simplify_error_request(simplify_error, simplify)
         texture = self._texture_option(texture)
         if texture is not None:
             texture = {"threshold": threshold, **texture}
@@ -1253,7 +1282,11 @@ class ImplicitSurface(nn.Module):
             mesh = ops.marching_cubes(u, threshold)
         vertices, triangles = mesh
         if simplify is not None:
+            full = (vertices, triangles) if simplify_error is not None else None
             vertices, triangles, _, self.last_simplify_stats = ops.simplify_mesh(vertices, triangles, simplify, origin=(-0.5, -0.5, -0.5))
+            if full is not None:
+                self.last_simplify_stats["error"] = ops.mesh_distance(*full, vertices, triangles, **simplify_error)
+                del full
         b_max, b_min = bound_max.detach().cpu().numpy(), bound_min.detach().cpu().numpy()
         attrs = tex = None
         if attributes or texture is not None:          # on the device-resident vertices; span: the host expression's (float32) difference, widened
@@ -1272,7 +1305,7 @@ class ImplicitSurface(nn.Module):
     def validate(self, rays_o, rays_d, near, far, volumes, mask_volumes, imgs, features, match_features, intrs, c2ws, bound_min, bound_max,
                  hw, cos_anneal_ratio=1.0, step=None, extract_geometry=True, mesh_resolution=512, threshold=0.0, scene=None, shard=None, sparse=None,
                  sparse_mesh=None, mesh_attributes=None, surface_render=None, surface_fusion=None, mesh_simplify=None, mesh_texture=None,
-                 mesh_render=None):
+                 mesh_render=None, mesh_simplify_error=None):
         """shard (gens_amd.distributed.Shard, optional): render only this rank's contiguous ray range and evaluate only its lattice
         chunks; the (P, 8) image buffer / the lattice slabs are gathered over RCCL, so every rank returns the whole image.  The jitter
         of EVERY ray is drawn on every rank from the identically seeded CPU generator (the reference's draw order) and sliced with
@@ -1285,7 +1318,10 @@ class ImplicitSurface(nn.Module):
         and views) is traced to the surface and the depth maps are fused into a point cloud (fuse_surface, K32) -> outputs["fused_points"],
         ["fused_normals"], ["fused_colors"], ["fused_seen"]; not with a shard.  mesh_simplify: extract_geometry's `simplify` (a cell edge in
         lattice spacings; default: the attribute of that name, None / False / 0 = off): outputs["vertices"], ["triangles"] and the vertex
-        attributes are those of the simplified mesh (K33); self.last_simplify_stats holds its counts.  mesh_texture: extract_geometry's
+        attributes are those of the simplified mesh (K33); self.last_simplify_stats holds its counts.  mesh_simplify_error: extract_geometry's
+        `simplify_error` (True or a dict of ops.mesh_distance's keywords; default: the attribute of that name, None / False = off): the
+        simplified mesh is measured against the extracted one (K36) into self.last_simplify_stats["error"]; ValueError before any launch
+        when the simplification is off.  mesh_texture: extract_geometry's
         `texture` with this scene's views (the tile edge in texels or a dict of texture_mesh's keywords; default: the attribute of that name,
         None / False / 0 = off) -> outputs["texture"], ["texture_seen"], ["texture_uv"] (K34), which save_validation_outputs writes as an
         OBJ beside the PLY.  mesh_render (default: the attribute of that name, None / False = off; True, or a dict of render_mesh's keywords
@@ -1304,6 +1340,7 @@ class ImplicitSurface(nn.Module):
             if "normals" not in ((asked,) if isinstance(asked, str) else tuple(asked or ())):
                 raise ValueError("mesh_render: smooth shading needs mesh_attributes with \"normals\"")
         mesh_simplify = self._simplify_request(mesh_simplify) if extract_geometry else None      # (refused before anything is launched)
+        mesh_simplify_error = self._simplify_error_request(mesh_simplify_error, mesh_simplify) if extract_geometry else None
         mesh_texture = self._texture_option(mesh_texture) if extract_geometry else None
         surface_fusion = self.surface_fusion if surface_fusion is None else surface_fusion
         if surface_fusion:
@@ -1336,7 +1373,8 @@ class ImplicitSurface(nn.Module):
             t_geo = time.perf_counter()
             mesh = self.extract_geometry(scene.volumes_nograd(), bound_min, bound_max, mesh_resolution, threshold, shard=shard, sparse=sparse,
                                          sparse_mesh=sparse_mesh, attributes=mesh_attributes, views=scene.views,
-                                         simplify=0 if mesh_simplify is None else mesh_simplify, texture=0 if mesh_texture is None else mesh_texture)
+                                         simplify=0 if mesh_simplify is None else mesh_simplify, texture=0 if mesh_texture is None else mesh_texture,
+                                         simplify_error=False if mesh_simplify_error is None else mesh_simplify_error)
             outputs["vertices"], outputs["triangles"] = mesh[0], mesh[1]
             for name, values in ((mesh[2] or {}) if len(mesh) >= 3 else {}).items():
                 outputs["vertex_" + name] = values

@@ -66,7 +66,7 @@ const char* gens_last_error(void);
  *       and K30's gens_vertex_points, gens_vertex_pack, and K31's gens_trace_begin, gens_trace_march, gens_trace_refine, gens_trace_gather,
  *       gens_surface_pack, and K32's gens_fuse_depth_maps, gens_fused_points, and K33's gens_cluster_keys, gens_cluster_triangles,
  *       gens_cluster_solve, and K34's gens_texture_points, gens_texture_snap, gens_texture_keep_better,
- *       gens_texture_pack, gens_texture_uv, and K35's gens_mesh_shade. */
+ *       gens_texture_pack, gens_texture_uv, and K35's gens_mesh_shade, and K36's gens_mesh_closest_point. */
 int gens_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -1250,6 +1250,74 @@ typedef struct {
     uint8_t *img, *seen;
 } gens_mesh_shade_args;
 int gens_mesh_shade(const gens_mesh_shade_args* args, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * K36  Exact point-to-mesh distance: for every query the nearest point of a triangle mesh, over K23's gens_mesh_grid
+ *      (ops.closest_point_on_mesh, ops.mesh_distance, io.compare_meshes, python -m gens_amd.compare_meshes,
+ *      ImplicitSurface.extract_geometry(simplify_error=)), csrc/k36_mesh_distance.hip.  tests/mesh_distance_reference.py restates all of it
+ *      in numpy, as brute force over all faces.
+ *
+ *   Definition.  Arithmetic is float64, every operation rounded on its own, in the order written; the quotients are the correctly rounded
+ *   ones; there is no square root.  dot(u, v) = (u_x v_x + u_y v_y) + u_z v_z.  q is the query; a, b, c are the corners of face f in stored
+ *   order.  Differences, products with a scalar and sums of points are per component.
+ *     (a) d2(q, f), the closest point p(q, f) and the region code -- the region walk of Ericson, Real-Time Collision Detection, 5.1.5.
+ *         ab = b - a,  ac = c - a,  ap = q - a;  n = ab x ac = (ab_y ac_z - ab_z ac_y,  ab_z ac_x - ab_x ac_z,  ab_x ac_y - ab_y ac_x).
+ *         If n_x == 0 and n_y == 0 and n_z == 0 the face is DEGENERATE: the degenerate path below.  Otherwise
+ *           d1 = dot(ab, ap), d2' = dot(ac, ap);  bp = q - b:  d3 = dot(ab, bp), d4 = dot(ac, bp);  cp = q - c:  d5 = dot(ab, cp),
+ *           d6 = dot(ac, cp);  vc = d1 d4 - d3 d2',  vb = d5 d2' - d1 d6,  va = d3 d6 - d5 d4;  e = d4 - d3,  g = d5 - d6
+ *         and the FIRST of these tests that holds decides (all of them non-strict, <= and >=, so a query on a border between two regions
+ *         belongs to the earlier one):
+ *           1. d1 <= 0 and d2' <= 0:                region 1 (vertex a),  p = a
+ *           2. d3 >= 0 and d4 <= d3:                region 2 (vertex b),  p = b
+ *           3. vc <= 0 and d1 >= 0 and d3 <= 0:     region 4 (edge ab),   den = d1 - d3,  v = d1 / den,  p = a + v ab
+ *           4. d6 >= 0 and d5 <= d6:                region 3 (vertex c),  p = c
+ *           5. vb <= 0 and d2' >= 0 and d6 <= 0:    region 6 (edge ca),   den = d2' - d6,  w = d2' / den,  p = a + w ac
+ *           6. va <= 0 and e >= 0 and g >= 0:       region 5 (edge bc),   den = e + g,  w = e / den,  p = b + w (c - b)
+ *           7. va >= 0 and vb >= 0 and vc >= 0:     region 0 (interior),  den = (va + vb) + vc,  v = vb / den,  w = vc / den,
+ *                                                   p = (a + v ab) + w ac
+ *         A quotient is formed only where its den > 0 (STRICT): where the deciding test is 3, 5, 6 or 7 and den > 0 is false, and where no
+ *         test holds (rounding can leave va, vb, vc with signs that no point of the plane has), the degenerate path is taken.  So no
+ *         division yields a NaN for finite input whose products stay in range, every v and w lies in 0 .. 1, and p lies in the face up to
+ *         the rounding of its own sums.  Then  u = q - p,  d2 = (u_x u_x + u_y u_y) + u_z u_z.
+ *         The degenerate path, region 7: for the segments (a, b), (b, c), (c, a) in this order, (p0, p1) with e = p1 - p0:  l = dot(e, e);
+ *         t = dot(q - p0, e) / l if l > 0, else 0 (a segment of zero length is its end point);  t = 0 unless t > 0;  t = 1 if t > 1;
+ *         s = p0 + t e;  its d2 as above.  The smallest d2 wins, the first segment on ties (a later one replaces only with <).
+ *     (b) The result of a query is the lexicographically smallest (d2, f) over ALL faces f of the mesh, a face whose d2 is NaN left out (a
+ *         brute-force definition: the grid is only how the kernel finds it), with p and the region of that face.  With max_dist finite the
+ *         result stands only if d2 <= max_dist max_dist (one rounded product; NON-strict and on squares -- K24's gens_nearest_point takes the
+ *         root and keeps d < max_dist, strictly, as the DTU script does; this one has no root to take).  Otherwise, and for a mesh without
+ *         faces:  d2 = +inf,  face = -1,  p = (NaN, NaN, NaN),  region = 255.  A query with a coordinate that is not finite:  d2 = NaN and the
+ *         same face, p and region.
+ *   The walk.  The query's cell is floor((q - lo) (1 / cell)) per axis clamped into the grid (lo and cell widened from float32, as
+ *     gens_mesh_grid_count computes a face's cells).  For r = 0, 1, 2, ... the cells at Chebyshev distance exactly r from it that lie in
+ *     the grid are visited, none twice.  gens_mesh_grid_count lists a face in every cell its AABB overlaps, widened OUTWARDS by 1e-5 cell, so
+ *     a face listed in no cell of the block [c - r, c + r]^3 lies wholly beyond one of the block's sides, by at least 1e-5 cell less the
+ *     rounding of its cell coordinates (at most 512 x 4 x 2^-53 < 3e-13 cell); a face clamped into a border cell is listed there, so the
+ *     sides on the grid's border have nothing beyond them.  bound = the smallest, over the block's sides that are not on the border, of
+ *     max(s (1 - 2^-40) - 2^-30, 0) cells, s = the side's coordinate less the query's (or the reverse) in cells, times cell.  The margin
+ *     covers the rounding of the query's cell coordinate ((|s| + 513) 4 x 2^-53 cells), of 1 / cell and of bound^2, and of d2: the p of
+ *     the rule lies within 4 x 2^-53 x (the largest |coordinate| of the face) of the face, which is below 1e-5 cell while
+ *     (|lo| + 512 cell) / cell < 2^32 -- checked, GENS_ELIMIT; ops.build_mesh_grid's boxes stay below 2^29.  The widening of the lists is
+ *     therefore slack on top of the margin, not something the margin has to win back.  The walk stops after ring r when the best
+ *     d2 < bound^2, STRICTLY: every unvisited face then has a larger d2, so none can win, and none can tie and win on its index -- with <=
+ *     a face with an equal d2 and a smaller index, one ring further out, would change the answer.  It also stops when
+ *     bound^2 > max_dist^2 (nothing unvisited can pass the cap) and when the block covers the grid: after at most max(nx, ny, nz) rings.
+ *     A face listed in several cells is evaluated once per listing met; d2 is a pure function of (q, f), so that changes nothing.
+ *   NOT promised: a sign, a distance to anything but the triangles as stored, a cost bound for queries far from every face (a query at the
+ *     centre of a sphere reads every cell of the grid; a coarse level over the grid would bound that and is not built).
+ *
+ *   gens_mesh_closest_point: one thread per query.  grid: as ops.build_mesh_grid / gens_mesh_grid_{count,fill} make it (vertex indices
+ *     < V are the caller's check, as for every user of the grid; face ids in cell_faces outside 0 .. n_faces - 1 and list bounds outside
+ *     0 .. cell_start[cells] are skipped, never read through).  queries (n, 3) float64; dist2 (n) float64; face (n) int32; optional (NULL:
+ *     not written) point (n, 3) float64 and region (n) uint8.  All device pointers.
+ *   Arguments are checked before any launch.  GENS_EINVAL: a null grid; n_queries < 0; n_faces < 0; max_dist not > 0 (a NaN included; +inf:
+ *     no cap); with n_queries > 0, null queries, dist2 or face; with faces too, a null pointer in the grid.  GENS_ELIMIT: n_queries or
+ *     n_faces >= 2^31; a grid outside K23's limits (1 .. 512 cells per axis, a positive finite cell, a finite corner) or the ratio above.
+ *     n_queries == 0 succeeds without a launch.  n_faces == 0 does not launch the walk: one fill writes the results of (b).
+ *     The ABI version stays 12: no existing entry changes.
+ * ---------------------------------------------------------------------------------------------------------- */
+int gens_mesh_closest_point(const gens_mesh_grid* grid, const double* queries, int64_t n_queries, double max_dist, double* dist2,
+                            int32_t* face, double* point /* (n, 3) or NULL */, uint8_t* region /* or NULL */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K14  C (m x n) = A^T B for tall row-major operands A (k x m), B (k x n), k >> m, n: the weight-gradient product of the training
