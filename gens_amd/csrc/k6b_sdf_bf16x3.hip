@@ -48,6 +48,54 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 #define GB_SLOTS 2048                       // (XCC 3 bits, SE 2, CU 4, wave 2)
 #define GB_C 144.26950408889634f            // 100 / ln 2: hidden units travel as c * softplus (k6_sdfmlp.hip::softplus_t)
 
+// Where a wave issues its refill of the weight ring (GB_BOUNDARY and GB_FILL in the kernel):
+//   1  in the gaps behind the first MFMAs after the chunk boundary, one piece per gap (the shipped placement)
+//   0  at the boundary itself, back to back in front of those MFMAs (what profiles/r25_k6b_stamps.txt stamped; kept for that A/B)
+// The MFMAs, their operands and their order are the same in both, and so is every result bit (profiles/r25_sdf_ring_boundaries.txt).
+#ifndef GENS_K6B_PLACE
+#define GENS_K6B_PLACE 1
+#endif
+// The five-level gradient kernel keeps placement 0: it holds 508 of 512 registers, and with the refill between its MFMAs it spills.
+#define GB_PLACE(NLEV_, GRAD_) ((GRAD_) && (NLEV_) == 5 ? 0 : GENS_K6B_PLACE)
+
+// Cycle stamps of the gradient kernel's phases (build with -DGENS_K6B_STAMPS: make -C gens_amd/csrc stamps; scripts/probe/k6b_stamps_probe.py
+// reads them): never in the shipped library.  GB_STAMP(K_) ends a stretch of kind K_: 0 products (MFMAs, their LDS reads, whatever sits in
+// their gaps), 1 a boundary's vmcnt wait, 2 its barrier, 3 its refill issues, 4 a forward layer's softplus and split, 5 a reverse layer's
+// product with softplus' and split, 6 the chain rule to x.  Every wave adds its cycles per kind into k6b_stamps[wave][K_], the number of
+// stamps of that kind into [wave][8 + K_], the cost of one stamp (two back to back) into [wave][7] and one into [wave][15].
+#ifdef GENS_K6B_STAMPS
+__device__ unsigned long long k6b_stamps[GB_WAVES][16];
+#define GB_STAMP_READ(T_)                                                                  \
+    __builtin_amdgcn_sched_barrier(0);                                                     \
+    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(T_)::"memory");             \
+    __builtin_amdgcn_sched_barrier(0);
+#define GB_STAMP_INIT()                                                                    \
+    unsigned long long st_sum[8] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull}, st_last, st_now; \
+    int st_cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};                                              \
+    GB_STAMP_READ(st_last)                                                                 \
+    GB_STAMP_READ(st_now)                                                                  \
+    st_sum[7] = st_now - st_last;                                                          \
+    st_last = st_now;
+#define GB_STAMP(K_)                                                                       \
+    {                                                                                      \
+        GB_STAMP_READ(st_now)                                                              \
+        st_sum[K_] += st_now - st_last;                                                    \
+        st_last = st_now;                                                                  \
+        ++st_cnt[K_];                                                                      \
+    }
+#define GB_STAMP_WRITE()                                                                   \
+    if (lane == 0) {                                                                       \
+        _Pragma("unroll") for (int k_ = 0; k_ < 8; ++k_) {                                 \
+            atomicAdd(&k6b_stamps[wave][k_], st_sum[k_]);                                  \
+            atomicAdd(&k6b_stamps[wave][8 + k_], k_ < 7 ? (unsigned long long)st_cnt[k_] : 1ull); \
+        }                                                                                  \
+    }
+#else
+#define GB_STAMP_INIT()
+#define GB_STAMP(K_)
+#define GB_STAMP_WRITE()
+#endif
+
 #define GB_PUT(BLK_, W_, A_, B_)                                            \
     {                                                                       \
         const Split3Word sw__ = split3_pair((A_), (B_));                    \
@@ -156,6 +204,7 @@ __global__ __launch_bounds__(64 * GB_WAVES, GB_OCC(NLEV, GRAD)) void sdf_bf16x3_
     // those of the one-wave build
     constexpr bool DIET = GB_OCC(NLEV, GRAD) == 2;
     constexpr int GT = DIET ? 1 : GB_GT;
+    constexpr int PLACE = GB_PLACE(NLEV, GRAD);
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -169,14 +218,15 @@ __global__ __launch_bounds__(64 * GB_WAVES, GB_OCC(NLEV, GRAD)) void sdf_bf16x3_
     // the stream is a scalar, 16 lane the one vector offset, lane i lands at the piece's base in LDS + 16 i)
     const __amdgpu_buffer_rsrc_t prs = __builtin_amdgcn_make_buffer_rsrc((void*)pieces, 0, NCHUNK * GB_CH * GB_PIECE, 0x00020000);
     const uint32_t lane16 = (uint32_t)lane * 16u;
-    auto stage = [&](int c) {
+    auto stage1 = [&](int c, int p) {      // this wave's p-th piece of chunk c
         char* dst = lds + (c % GB_RING) * (GB_CH * GB_PIECE);
+        const int piece = wave + GB_WAVES * p;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(prs, (__attribute__((address_space(3))) void*)(dst + piece * GB_PIECE), 16, lane16,
+                                                 (uint32_t)(c * (GB_CH * GB_PIECE) + piece * GB_PIECE), 0, 0);
+    };
+    auto stage = [&](int c) {
 #pragma unroll
-        for (int p = 0; p < GB_LPW; ++p) {
-            const int piece = wave + GB_WAVES * p;
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(prs, (__attribute__((address_space(3))) void*)(dst + piece * GB_PIECE), 16, lane16,
-                                                     (uint32_t)(c * (GB_CH * GB_PIECE) + piece * GB_PIECE), 0, 0);
-        }
+        for (int p = 0; p < GB_LPW; ++p) stage1(c, p);
     };
 #pragma unroll
     for (int c = 0; c < GB_RING - 1; ++c) stage(c);
@@ -272,20 +322,46 @@ __global__ __launch_bounds__(64 * GB_WAVES, GB_OCC(NLEV, GRAD)) void sdf_bf16x3_
     u32x4 abuf[2][GB_TERMS * GT];      // A operands: this group's and the next one's
     int par = 0;                   // (compile-time after unrolling, like every index below)
     int dirty = GRAD ? 1 : 0;      // stores are outstanding: the next chunk boundary waits for everything
+    int pend = -1, pend_i = 0;     // the chunk whose refill the last boundary left to the MFMA gaps, and this wave's next piece of it
+    GB_STAMP_INIT()
 
     // chunk boundary: this wave's share of chunk C_ has landed (its later chunks may still be in flight), every wave says so, and the
     // ring slot everyone has just finished reading is refilled three chunks ahead
+    //
+    // The refill is not issued at the boundary (PLACE 1): the boundary leaves it pending (pend, pend_i) and the MFMAs that follow
+    // issue it one piece per MFMA gap (GB_FILL).  INVARIANT: when boundary c begins its wait, this wave has issued all its pieces of every
+    // chunk <= min(c + GB_RING - 2, NCHUNK - 1) and of no later one -- a refill still pending then (two boundaries with no MFMA between them:
+    // the first two loads of a segment) is issued there, in front of the wait -- so the vmcnt immediates below count exactly the later__
+    // chunks of GB_LPW loads that may stay in flight, and after the wait this wave's pieces of chunk c have landed.  (Stash loads and stores
+    // in flight only make the wait longer: buffer loads return in order, and `dirty` waits for everything.)
+#define GB_PEND_FLUSH()                                                                                  \
+    while (pend >= 0) {                                                                                  \
+        stage1(pend, pend_i);                                                                            \
+        if (++pend_i == GB_LPW) pend = -1;                                                               \
+    }
 #define GB_BOUNDARY(C_)                                                                                  \
     {                                                                                                    \
         const int c__ = (C_);                                                                            \
         const int later__ = (c__ + GB_RING - 2 < NCHUNK - 1 ? c__ + GB_RING - 2 : NCHUNK - 1) - c__;     \
+        GB_PEND_FLUSH()                                                                                  \
+        GB_STAMP(0)                                                                                      \
         if (dirty || later__ <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                      \
         else if (later__ == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GB_LPW) : "memory");             \
         else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * GB_LPW) : "memory");                           \
         dirty = 0;                                                                                       \
+        GB_STAMP(1)                                                                                      \
         __builtin_amdgcn_s_barrier();                                                                    \
         asm volatile("" ::: "memory");                                                                   \
-        if (c__ + GB_RING - 1 < NCHUNK) stage(c__ + GB_RING - 1);                                        \
+        GB_STAMP(2)                                                                                      \
+        if (c__ + GB_RING - 1 < NCHUNK) {                                                                \
+            if (PLACE == 0) {                                                                            \
+                stage(c__ + GB_RING - 1);                                                                \
+                GB_STAMP(3)                                                                              \
+            } else {                                                                                     \
+                pend = c__ + GB_RING - 1;                                                                \
+                pend_i = 0;                                                                              \
+            }                                                                                            \
+        }                                                                                                \
     }
     // pieces P0_ .. P0_ + CNT_ -> A register set SET_
 #define GB_LOAD(SET_, P0_, CNT_)                                                                         \
@@ -294,14 +370,23 @@ __global__ __launch_bounds__(64 * GB_WAVES, GB_OCC(NLEV, GRAD)) void sdf_bf16x3_
         if (p_ % GB_CH == 0) GB_BOUNDARY(p_ / GB_CH)                                                     \
         abuf[SET_][j_] = *((const u32x4*)(lds + ((p_ / GB_CH) % GB_RING) * (GB_CH * GB_PIECE) + (p_ % GB_CH) * GB_PIECE) + lane); \
     }
-#define GB_MFMA(ACC_, A_, B_) ACC_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, (A_)), __builtin_bit_cast(bf16x8, (B_)), ACC_, 0, 0, 0)
+    // the gap behind one MFMA: one piece of a pending refill -- an LDS-direct issue is the one long filler a gap has room for
+#define GB_FILL()                                                                                        \
+    if (pend >= 0) {                                                                                     \
+        __builtin_amdgcn_sched_barrier(0);                                                               \
+        stage1(pend, pend_i);                                                                            \
+        if (++pend_i == GB_LPW) pend = -1;                                                               \
+        __builtin_amdgcn_sched_barrier(0);                                                               \
+    }
+#define GB_MFMA_(ACC_, A_, B_) ACC_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, (A_)), __builtin_bit_cast(bf16x8, (B_)), ACC_, 0, 0, 0)
+#define GB_MFMA(ACC_, A_, B_) { GB_MFMA_(ACC_, A_, B_); GB_FILL() }
     // accumulator of output tile T_ of a reverse K block: hidden tiles, conditioning tiles, the point-encoding tile
 #define GB_RACC(T_) (*((T_) < 4 ? &acc[(T_) < 4 ? (T_) : 0] : (T_) < 4 + TC ? &gc[(T_) < 4 + TC && (T_) >= 4 ? (T_) - 4 : 0] : &gp))
     // the six products of one operand pair, smallest first: weight term WA_ x activation term WB_
 #define GB_TERM(WA_, WB_, REV_, B_)                                                                      \
     _Pragma("unroll") for (int t_ = 0; t_ < GT; ++t_) if (t_ < nt_) {                                    \
-        if (REV_) GB_MFMA(GB_RACC(t0_ + t_), abuf[par][GB_TERMS * t_ + (WA_)], (B_)[i_].p[(WB_)]);       \
-        else GB_MFMA(acc[(t0_ + t_) & 3], abuf[par][GB_TERMS * t_ + (WA_)], (B_)[i_].p[(WB_)]);          \
+        if (REV_) GB_MFMA(GB_RACC(t0_ + t_), abuf[par][GB_TERMS * t_ + (WA_)], (B_)[i_].p[(WB_)])        \
+        else GB_MFMA(acc[(t0_ + t_) & 3], abuf[par][GB_TERMS * t_ + (WA_)], (B_)[i_].p[(WB_)])           \
     }
     // CNT_ K blocks of NT_ output tiles from piece P0_ on, B operands B_[0 .. CNT_); REV_: the accumulators of a reverse block.  The A
     // operands arrive in groups of GT tiles (three terms each), one group ahead of the MFMAs that read them.  Within a group the
@@ -376,6 +461,7 @@ __global__ __launch_bounds__(64 * GB_WAVES, GB_OCC(NLEV, GRAD)) void sdf_bf16x3_
             }
             GB_SEGMENT(S::fwd(l) + S::BLK * (NC + (l == 3 ? 2 : 0)), 8, 4, H, false);
         }
+        GB_STAMP(0)
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             f32x16 h, d;
@@ -412,6 +498,7 @@ __global__ __launch_bounds__(64 * GB_WAVES, GB_OCC(NLEV, GRAD)) void sdf_bf16x3_
                 if constexpr (GRAD) GB_SPLIT_TILE(t, g);
             }
         }
+        GB_STAMP(4)
     }
     // not-a-number inputs must come out as not-a-number (the reference's layers propagate them; the max / median forms of the activation drop
     // them): a poison term 0 * (sum of the inputs), NaN iff one of them is NaN or infinite
@@ -455,6 +542,7 @@ __global__ __launch_bounds__(64 * GB_WAVES, GB_OCC(NLEV, GRAD)) void sdf_bf16x3_
                 GB_SEGMENT(S::rev(l), 8, 4 + TC, H, true);
             }
             // G_{l-1} = (W_l^T G_l) * softplus'(a_{l-1})
+            GB_STAMP(0)
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 f32x16 g;
@@ -473,6 +561,7 @@ __global__ __launch_bounds__(64 * GB_WAVES, GB_OCC(NLEV, GRAD)) void sdf_bf16x3_
                 }
                 GB_SPLIT_TILE(t, g);
             }
+            GB_STAMP(5)
         }
         {   // layer 0 reads the point encoding only: the six products in five independent chains, added smallest first at the end
             GB_ZERO();
@@ -481,15 +570,16 @@ __global__ __launch_bounds__(64 * GB_WAVES, GB_OCC(NLEV, GRAD)) void sdf_bf16x3_
             for (int i = 0; i < 8; ++i) {
                 if (i + 1 < 8) { GB_LOAD(par ^ 1, S::rev(0) + GB_TERMS * (i + 1), GB_TERMS) }
                 __builtin_amdgcn_sched_barrier(0);
-                GB_MFMA(acc[0], abuf[par][2], H[i].p[0]);
-                GB_MFMA(acc[1], abuf[par][1], H[i].p[1]);
-                GB_MFMA(acc[2], abuf[par][1], H[i].p[0]);
-                GB_MFMA(acc[0], abuf[par][0], H[i].p[2]);
-                GB_MFMA(acc[3], abuf[par][0], H[i].p[1]);
-                GB_MFMA(gp, abuf[par][0], H[i].p[0]);
+                GB_MFMA(acc[0], abuf[par][2], H[i].p[0])
+                GB_MFMA(acc[1], abuf[par][1], H[i].p[1])
+                GB_MFMA(acc[2], abuf[par][1], H[i].p[0])
+                GB_MFMA(acc[0], abuf[par][0], H[i].p[2])
+                GB_MFMA(acc[3], abuf[par][0], H[i].p[1])
+                GB_MFMA(gp, abuf[par][0], H[i].p[0])
                 __builtin_amdgcn_sched_barrier(0);
                 par ^= 1;
             }
+            GB_STAMP(0)
 #pragma unroll
             for (int r = 0; r < 16; ++r) gp[r] += (acc[0][r] + acc[1][r]) + (acc[2][r] + acc[3][r]);
         }
@@ -542,10 +632,15 @@ __global__ __launch_bounds__(64 * GB_WAVES, GB_OCC(NLEV, GRAD)) void sdf_bf16x3_
                 grad_out[3 * src + 2] = g[2] * inv_scale;
             }
         }
+        GB_STAMP(6)
+        GB_STAMP_WRITE()
         if (lane == 0) atomicExch(lock, 0u);
     }
+#undef GB_PEND_FLUSH
 #undef GB_BOUNDARY
 #undef GB_LOAD
+#undef GB_FILL
+#undef GB_MFMA_
 #undef GB_MFMA
 #undef GB_RACC
 #undef GB_TERM
@@ -641,3 +736,13 @@ extern "C" int gens_sdf_bf16x3_residency(int n_levels, int grad, int out[4]) {
     out[3] = blocks;
     return 0;
 }
+
+#ifdef GENS_K6B_STAMPS
+extern "C" int gens_debug_k6b_stamps(unsigned long long* out, int reset) {
+    if (reset) {
+        unsigned long long z[GB_WAVES * 16] = {0};
+        return hipMemcpyToSymbol(HIP_SYMBOL(k6b_stamps), z, sizeof(z)) == hipSuccess ? 0 : 1;
+    }
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(k6b_stamps), sizeof(unsigned long long) * GB_WAVES * 16) == hipSuccess ? 0 : 1;
+}
+#endif
