@@ -22,8 +22,20 @@
 //   * the weight stream is one sequence of GROUPS of three 1 KB pieces (64 lanes x 16 bytes): a bf16 group is the three planes of one
 //     (M tile, K block); the first group is the float32 fragments [ray_dir_fc.0 | ray_dir_fc.2 tile 0 | tile 1] and the last one
 //     [rgb_fc.0 quads 8, 9 | rgb_fc.2 | 0] in K7t's float4 layout.  Every lane loads its 48 bytes of a group two groups ahead.
+//   * THREE waves per SIMD (KB_OCC, <= 168 registers, no scratch): the kernel is bound by the vector pipe and its dataflow is one register
+//     chain, so a third resident wave fills issue slots the two leave empty (profiles/r26_blend_three_waves.txt: vector issue 63 -> 75 % of the
+//     SIMD cycles, 2 716 -> 2 336 us per launch of 3.9 M points x 4 views, the same output bits).  DIET in the kernel: the
+//     values phase 0 left in LDS and that are used late -- the colour, the ray difference's rgb_fc.0 quads, the mask -- are read again
+//     where they are used and not carried from the prologue.  -DGENS_K7B_OCC=2 is the build before it, instruction for instruction.
 #include "k7t_rows.h"
 #include "split3.h"
+
+// resident waves per SIMD the kernel is bounded for (__launch_bounds__(64, w): w workgroups of one wave per SIMD): 3 wants <= 168 registers,
+// 2 <= 256.  Per instantiation, so that one that would spill at 3 can stay at 2; today none does.
+#ifndef GENS_K7B_OCC
+#define GENS_K7B_OCC 3
+#endif
+#define KB_OCC(NLEV_, S_) (GENS_K7B_OCC)
 
 struct BlendBWeights {
     const u32x4* stream;        // groups in consumption order: 3 pieces x 64 lanes x 16 bytes each
@@ -43,7 +55,7 @@ __device__ __forceinline__ f32x4 elu4b(f32x4 x) {
 }
 
 template <int NLEV, int S>
-__global__ __launch_bounds__(64, 2) void blend_b_k(BlendBWeights W, MapSet fs, const float4* __restrict__ imgs, const float* __restrict__ w2c,
+__global__ __launch_bounds__(64, KB_OCC(NLEV, S)) void blend_b_k(BlendBWeights W, MapSet fs, const float4* __restrict__ imgs, const float* __restrict__ w2c,
                                                    const float* __restrict__ intr, const float* __restrict__ c2w, const float* __restrict__ pts,
                                                    const int64_t* __restrict__ index, int64_t n_max, const int32_t* __restrict__ n_dev,
                                                    float* __restrict__ rgb_out, uint8_t* __restrict__ vis_out) {
@@ -56,6 +68,9 @@ __global__ __launch_bounds__(64, 2) void blend_b_k(BlendBWeights W, MapSet fs, c
     constexpr int NPT = PPW / 16;            // N tiles of POINTS of the per-point product (mean / variance columns)
     static_assert(S >= 2 && S <= 4, "two to four source views");
     static_assert(4 * XQ <= KT_XS && XQ <= 8, "feature tile too narrow");
+    // DIET: the build for three waves per SIMD, <= 168 registers: rgbc, rdsh, rd3one and (for its late uses) mask are not carried through
+    // the network but read again from X, RD and R, which phase 0 writes and nothing overwrites (ds_bpermute moves registers only)
+    constexpr bool DIET = KB_OCC(NLEV, S) >= 3;
     __shared__ float X[64 * KT_XS];          // gathered rows: rgb (3), features (4 NLEV), one
     __shared__ float RD[64 * 5];             // ray difference (4)
     __shared__ float R[64];                  // mask
@@ -88,13 +103,17 @@ __global__ __launch_bounds__(64, 2) void blend_b_k(BlendBWeights W, MapSet fs, c
         const int row = 16 * j + np;
 #pragma unroll
         for (int kq = 0; kq < XQ; ++kq) xq[j][kq] = X[row * KT_XS + 4 * kq + q];
-        rgbc[j] = xq[j][0];
         rdq[j] = RD[row * 5 + q];
         dotv[j] = RD[row * 5 + 3];
         mask[j] = R[row];
-        rdsh[j] = q ? RD[row * 5 + q - 1] : 0.0f;                      // rgb_fc.0's quad [vis, rd0, rd1, rd2] (vis filled in later)
-        rd3one[j] = q == 0 ? dotv[j] : (q == 1 ? 1.0f : 0.0f);        // ... and [rd3, one, 0, 0]
+        if constexpr (!DIET) {
+            rgbc[j] = xq[j][0];
+            rdsh[j] = q ? RD[row * 5 + q - 1] : 0.0f;                      // rgb_fc.0's quad [vis, rd0, rd1, rd2] (vis filled in later)
+            rd3one[j] = q == 0 ? dotv[j] : (q == 1 ? 1.0f : 0.0f);        // ... and [rd3, one, 0, 0]
+        }
     }
+    // DIET: this lane's row of N tile j_ for a late read (opaque lane: a new address to the compiler, or it keeps the prologue's value alive)
+#define KB_ROW_O(j_) (16 * (j_) + (lane_o & 15))
     const float* tab = W.tab + q * 8;
 #define KB_TAB(E, K) tab[(E) * 32 + (K)]
 #define KB_BIAS(E, T) ((f32x4){KB_TAB(E, 4 * (T)), KB_TAB(E, 4 * (T) + 1), KB_TAB(E, 4 * (T) + 2), KB_TAB(E, 4 * (T) + 3)})
@@ -328,6 +347,12 @@ __global__ __launch_bounds__(64, 2) void blend_b_k(BlendBWeights W, MapSet fs, c
 #pragma unroll
             for (int j = 0; j < KT_NT; ++j) XH[T][j] += elu4b(V2[T][j]);                    // x = x + x_res
     }
+    if constexpr (DIET) {
+        int lane_o = lane;
+        asm volatile("" : "+v"(lane_o));
+#pragma unroll
+        for (int j = 0; j < KT_NT; ++j) mask[j] = R[KB_ROW_O(j)];
+    }
 #pragma unroll
     for (int j = 0; j < KT_NT; ++j) vis[j] = hw_sigmoid(elu1t(vis[j] + W.v2_last_b)) * mask[j];
 
@@ -364,6 +389,17 @@ __global__ __launch_bounds__(64, 2) void blend_b_k(BlendBWeights W, MapSet fs, c
     float score[KT_NT];
     {
         f32x4 C1[KT_NT], C2[KT_NT];
+        if constexpr (DIET) {
+            int lane_o = lane;
+            asm volatile("" : "+v"(lane_o));
+            const int q_o = lane_o >> 4;
+#pragma unroll
+            for (int j = 0; j < KT_NT; ++j) {
+                const float* rd = RD + KB_ROW_O(j) * 5;
+                rdsh[j] = q_o ? rd[q_o - 1] : 0.0f;
+                rd3one[j] = q_o == 0 ? rd[3] : (q_o == 1 ? 1.0f : 0.0f);
+            }
+        }
 #define INIT_T_(j) zero4                                                                     // (bias: the one of quad 9)
 #define ACC_T_(j) C1[j]
         KB_PRODUCT(KT_NT, 1, 1, B_HB)                                                        // x's 32 columns
@@ -394,6 +430,12 @@ __global__ __launch_bounds__(64, 2) void blend_b_k(BlendBWeights W, MapSet fs, c
     }
 
     // ---------------------------------------------------------------- softmax over views, colour (:116-117)
+    if constexpr (DIET) {
+        int lane_o = lane;
+        asm volatile("" : "+v"(lane_o));
+#pragma unroll
+        for (int j = 0; j < KT_NT; ++j) rgbc[j] = X[KB_ROW_O(j) * KT_XS + (lane_o >> 4)];
+    }
 #pragma unroll
     for (int j = 0; j < KT_NT; ++j) {
         const float mx = group_max<G>(score[j]);
@@ -415,6 +457,41 @@ __global__ __launch_bounds__(64, 2) void blend_b_k(BlendBWeights W, MapSet fs, c
 #undef KB_F32
 #undef KB_SPLIT8
 #undef KB_DOT32
+#undef KB_ROW_O
+}
+
+// What the device says about one instantiation at the launcher's block size: registers per lane, scratch bytes per lane, static LDS bytes,
+// resident workgroups (of one wave) per CU.
+template <int S>
+static const void* blend_b_fn(int n_levels) {
+    switch (n_levels) {
+        case 1: return (const void*)blend_b_k<1, S>;
+        case 2: return (const void*)blend_b_k<2, S>;
+        case 3: return (const void*)blend_b_k<3, S>;
+        case 4: return (const void*)blend_b_k<4, S>;
+        default: return (const void*)blend_b_k<5, S>;
+    }
+}
+
+extern "C" int gens_blend_bf16x3_residency(int n_levels, int nv, int out[4]) {
+    GENS_CHECK_ARG(n_levels >= 1 && n_levels <= 5, GENS_ELIMIT, "gens_blend_bf16x3_residency: built for 1 to 5 feature levels, got %d", n_levels);
+    GENS_CHECK_ARG(nv >= 3 && nv <= 5, GENS_ELIMIT, "gens_blend_bf16x3_residency: built for two to four source views (nv = 3..5), got nv=%d", nv);
+    GENS_CHECK_ARG(out, GENS_EINVAL, "gens_blend_bf16x3_residency: null output");
+    const void* fn = nv == 3 ? blend_b_fn<2>(n_levels) : nv == 4 ? blend_b_fn<3>(n_levels) : blend_b_fn<4>(n_levels);
+    hipFuncAttributes attr;
+    int blocks = 0;
+    hipError_t err = hipFuncGetAttributes(&attr, fn);
+    if (err == hipSuccess) err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, 64, 0);
+    if (err != hipSuccess) {
+        (void)hipGetLastError();
+        gens_set_error("gens_blend_bf16x3_residency: %s", hipGetErrorString(err));
+        return (int)err;
+    }
+    out[0] = attr.numRegs;
+    out[1] = (int)attr.localSizeBytes;
+    out[2] = (int)attr.sharedSizeBytes;
+    out[3] = blocks;
+    return 0;
 }
 
 int gens_fill_maps(const char* who, MapSet* ms, const float* const* feats, const int* hw, int n_levels);

@@ -137,6 +137,7 @@ SIGNATURES = {
     "gens_blend_views_t_groups": [_i],
     "gens_blend_views_bf16x3": [_pp, _ip, _i, _p, _p, _p, _p, _i, _p, _p, _fp, _p, _p, _l, _p, _p, _p, _p],
     "gens_blend_bf16x3_groups": [_i],
+    "gens_blend_bf16x3_residency": [_i, _i, _ip],
     "gens_blend_pack_t": [_pp, _i, _p, _p, _p, _p],
     "gens_blend_views_t_dev": [_pp, _ip, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _l, _p, _p, _p, _p],
     "gens_compact_valid": [_p, _l, _p, _p, _p, _p],

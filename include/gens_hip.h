@@ -56,7 +56,7 @@ const char* gens_last_error(void);
  *       too), gens_select_views (the views of a fine-tune step out of the frozen maps and their layouts in one launch),
  *       gens_lookup_volume_bwd_bricks / _bwd2_bricks + gens_lookup_scatter_bricks_scratch_bytes (K2's volume-gradient scatter brick by brick).
  *       Later additions that change no existing entry keep 12: gens_sdf_{value,grad}_bf16x3 + gens_sdf_bf16x3_pieces (+ gens_sdf_bf16x3_residency),
- *       and K23's
+ *       gens_blend_bf16x3_residency, and K23's
  *       gens_mesh_grid_{count,fill}, gens_ray_first_hit, gens_view_rays_hit_faces, gens_face_cc_{hook,compress}, and K24's
  *       gens_mesh_sample_{count,emit}, gens_point_grid_{count,fill}, gens_radius_downsample_round, gens_nearest_point, and K25's
  *       gens_dilate_u8, gens_vertex_mask_votes, gens_view_rays_hit_counts, and K26's gens_filter_masks, gens_filter_band, gens_filter_levels,
@@ -565,6 +565,10 @@ int gens_blend_views_bf16x3(const float* const* feats, const int* hw, int n_leve
                             const float* c2w, int nv, const void* wstream, const float* tab, const float* scalars, const float* pts,
                             const int64_t* index, int64_t n, const int32_t* n_device, float* rgb_out, uint8_t* vis_out, void* stream);
 int gens_blend_bf16x3_groups(int n_levels);
+/* residency of gens_blend_views_bf16x3's kernel for n_levels (1..5) and nv (3..5) on the current device, at the launcher's block size (one
+ * wave): out[0] registers per lane (hipFuncAttributes.numRegs), out[1] scratch bytes per lane (localSizeBytes), out[2] static LDS bytes of a
+ * workgroup (sharedSizeBytes), out[3] resident workgroups per CU (hipOccupancyMaxActiveBlocksPerMultiprocessor).  out: HOST, 4 ints. */
+int gens_blend_bf16x3_residency(int n_levels, int nv, int out[4]);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K18  lookup_feature + BlendingNetwork.forward of a training / fine-tune step, and their backward
