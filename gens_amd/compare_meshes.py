@@ -1,10 +1,11 @@
-"""python -m gens_amd.compare_meshes A.{ply,obj} B.{ply,obj} [--density D | --samples N] [--max-dist M] [--json OUT] [--device D]
+"""python -m gens_amd.compare_meshes A.{ply,obj} B.{ply,obj} [--density D | --samples N] [--max-dist M] [--signed] [--json OUT] [--device D]
 
 The two-sided distance between two triangle meshes on the device (K36; io.compare_meshes, ops.mesh_distance): each mesh is sampled -- its
 vertices, then lattice points at spacing D on its triangles (default: about N = 1 000 000 per mesh) -- and every sample is given its exact
 distance to the other mesh.  Prints one line per direction (mean, RMS, maximum and quantiles, in the meshes' units) and the two summaries:
-the Hausdorff distance (the larger maximum) and the Chamfer distance (the mean of the two means).  Unsigned; samples with nothing within
-M are counted as unmatched and left out of the figures."""
+the Hausdorff distance (the larger maximum) and the Chamfer distance (the mean of the two means).  Unsigned unless --signed, which adds per
+direction the mean signed distance (positive on the side the other mesh's face normals point to), the samples inside and those without a sign
+(K37); samples with nothing within M are counted as unmatched and left out of the figures."""
 import argparse
 import json
 import sys
@@ -29,8 +30,11 @@ def compare_files(a, b, device=None, **kw):
 
 
 def format_direction(name, d):
-    return (f"{name}: n {d['n']}  mean {d['mean']:.6g}  rms {d['rms']:.6g}  max {d['max']:.6g}  q50 {d['q50']:.6g}  q90 {d['q90']:.6g}  "
+    line = (f"{name}: n {d['n']}  mean {d['mean']:.6g}  rms {d['rms']:.6g}  max {d['max']:.6g}  q50 {d['q50']:.6g}  q90 {d['q90']:.6g}  "
             f"q99 {d['q99']:.6g}  unmatched {d['unmatched']}")
+    if "signed_mean" in d:
+        line += f"  signed_mean {d['signed_mean']:.6g}  inside {d['inside']}  no_sign {d['no_sign']}"
+    return line
 
 
 def main(argv=None):
@@ -41,10 +45,13 @@ def main(argv=None):
     how.add_argument("--density", type=float, default=None, help="sample spacing on both meshes, in the meshes' units")
     how.add_argument("--samples", type=int, default=None, help="lattice samples per mesh, about (default 1000000): spacing sqrt(area / N)")
     ap.add_argument("--max-dist", type=float, default=None, help="samples with nothing within this distance are counted, not averaged")
+    ap.add_argument("--signed", action="store_true", help="also the signed mean, the samples inside and those without a sign, per direction")
     ap.add_argument("--json", default=None, metavar="OUT", help="also write the figures to this file")
     ap.add_argument("--device", default=None)
     args = ap.parse_args(argv)
     kw = {k: v for k, v in (("density", args.density), ("samples", args.samples), ("max_dist", args.max_dist)) if v is not None}
+    if args.signed:
+        kw["signed"] = True
     try:
         out = compare_files(args.a, args.b, device=args.device, **kw)
     except (ValueError, OSError, RuntimeError) as e:      # bad keywords or meshes; a file that cannot be read; a density too fine for the sampler

@@ -373,8 +373,9 @@ def simplify_mesh(vertices, triangles, cell, origin=None, normals=None, colors=N
 @torch.no_grad()
 def compare_meshes(va, ta, vb, tb, device=None, **kw):
     """ops.mesh_distance (K36: exact point-to-triangle distances, both ways) for host meshes, numpy in like the cleaners: vertices (V,3),
-    triangles (F,3) of the meshes A and B (arrays or tensors); kw: ops.mesh_distance's density, samples, max_dist -> its dict as plain Python
-    numbers (a_to_b / b_to_a with n, unmatched, mean, rms, max, q50, q90, q99; hausdorff; chamfer; density_a, density_b).  ValueError for what
+    triangles (F,3) of the meshes A and B (arrays or tensors); kw: ops.mesh_distance's density, samples, max_dist, signed -> its dict as plain
+    Python numbers (a_to_b / b_to_a with n, unmatched, mean, rms, max, q50, q90, q99 and, with signed=True, signed_mean, inside, no_sign (K37);
+    hausdorff; chamfer; density_a, density_b).  ValueError for what
     ops.mesh_distance refuses, for triangle indices outside the vertices and for vertices that are not finite, before the device is
     looked at."""
     from . import ops
@@ -397,6 +398,28 @@ def compare_meshes(va, ta, vb, tb, device=None, **kw):
     def plain(x):
         return {k: plain(v) for k, v in x.items()} if isinstance(x, dict) else (int(x) if isinstance(x, (int, np.integer)) else float(x))
     return plain(out)
+
+
+@torch.no_grad()
+def mesh_report(vertices, triangles, device=None):
+    """ops.mesh_topology(...).report() (K37) for a host mesh, numpy in like the cleaners: vertices (V,3), triangles (F,3) (arrays or tensors)
+    -> the dict of Python numbers: vertices, vertices_referenced, faces, faces_invalid, edges and their counts by class (boundary, manifold,
+    flipped, non-manifold), vertices_pinched, vertices_nonmanifold, components, largest_component_faces, boundary_components, euler, closed,
+    oriented, manifold, watertight, genus (None unless watertight), area, volume.  Any indices are accepted: a face with an index outside
+    the vertices or a repeated one is counted as invalid and takes part in nothing else.  ValueError, before the device is looked at, for
+    arrays that are not (n, 3), indices that are not whole numbers or do not fit int32."""
+    from . import ops
+    v_np, t_np = np.asarray(as_numpy(vertices)), np.asarray(as_numpy(triangles))
+    if any(x.size and (x.ndim != 2 or x.shape[1] != 3) for x in (v_np, t_np)):
+        raise ValueError(f"mesh_report: vertices {v_np.shape}, triangles {t_np.shape}: expected (V, 3) and (F, 3)")
+    if t_np.size and not np.issubdtype(t_np.dtype, np.integer):
+        raise ValueError(f"mesh_report: triangles of {t_np.dtype}: whole numbers")
+    if t_np.size and (t_np.min() < -2 ** 31 or t_np.max() >= 2 ** 31):
+        raise ValueError("mesh_report: a triangle index does not fit int32")
+    v_np = np.ascontiguousarray(v_np, dtype=np.float64).reshape(-1, 3)
+    t_np = np.ascontiguousarray(t_np.reshape(-1, 3), dtype=np.int32)
+    dev = device_of(vertices, triangles, device=device)
+    return ops.mesh_topology(torch.from_numpy(v_np).to(dev), torch.from_numpy(t_np).to(dev)).report()
 
 
 def dilate_masks(masks, radius=11):

@@ -251,6 +251,12 @@ SIGNATURES = {
     "gens_texture_uv": [_l, _i, _p, _p],
     "gens_mesh_shade": [C.POINTER(MeshShadeArgs), _p],
     "gens_mesh_closest_point": [C.POINTER(MeshGridArgs), _p, _l, _d, _p, _p, _p, _p, _p],
+    "gens_mesh_edge_keys": [_p, _l, _l, _p, _p, _p],
+    "gens_mesh_edge_classify": [_p, _p, _p, _p, _l, _l, _p, _p, _p, _p, _p, _p, _p],
+    "gens_mesh_fan_pairs": [_p, _l, _p, _p, _p, _l, _p, _p],
+    "gens_mesh_vertex_classify": [_p, _p, _p, _p, _p, _l, _l, _l, _p, _p, _p, _p],
+    "gens_mesh_pseudonormals": [_p, _p, _l, _l, _l, _p, _p, _p, _p, _p, _p, _p, _p],
+    "gens_mesh_distance_sign": [_p, _l, _p, _p, _p, _p, _p, _l, _l, _l, _p, _p, _p, _p, _p, _p, _p, _p],
 }
 
 _lib = None

@@ -112,6 +112,9 @@ class GenS(nn.Module):
         simplify_error = confs.get("mesh_simplify_error", None)  # optional: ... and measure the simplified mesh against the extracted one (ops.mesh_distance, K36); True or a dict of its keywords
         if simplify_error is not None:
             self.implicit_surface.mesh_simplify_error = simplify_error if isinstance(simplify_error, bool) else dict(simplify_error)
+        topology = confs.get("mesh_topology", None)             # optional: ... and take the topology report of the returned mesh (ops.mesh_topology, K37); True
+        if topology is not None:
+            self.implicit_surface.mesh_topology = bool(topology)
         texture = confs.get("mesh_texture", None)               # optional: extract_geometry / validate also return a texture atlas of the mesh (texture_mesh, K34); the tile edge in texels or its keywords
         if texture is not None:
             self.implicit_surface.mesh_texture = dict(texture) if hasattr(texture, "keys") else texture

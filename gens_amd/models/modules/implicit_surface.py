@@ -616,6 +616,19 @@ class ImplicitSurface(nn.Module):
             raise ValueError("simplify_error measures the simplified mesh against the extracted one: it needs simplify (a cell edge in lattice spacings)")
         return dict(simplify_error)
 
+    mesh_topology = None           # True: extract_geometry / validate take the topology report of the mesh they return (ops.mesh_topology, K37) ->
+                                   # last_mesh_topology.  None / False: off
+    last_mesh_topology = None      # ops.MeshTopology.report() of the mesh the last extract_geometry call returned (None: that call did not ask)
+
+    def _topology_request(self, topology):
+        """The topology report a mesh call asks for (None: the attribute `mesh_topology`) -> bool.  ValueError for anything but None or a bool."""
+        topology = self.mesh_topology if topology is None else topology
+        if topology is None:
+            return False
+        if not isinstance(topology, bool):
+            raise ValueError(f"topology = {topology!r}: True (None or False: off)")
+        return topology
+
     mesh_texture = None            # the tile edge in texels (3 to 64), or a dict of texture_mesh's keywords (texels, snap, max_move, chunk):
                                    # extract_geometry / validate also return a texture atlas of the mesh (texture_mesh, K34).  None / False / 0:
                                    # off (DESIGN.md, section 5k)
@@ -1228,7 +1241,7 @@ class ImplicitSurface(nn.Module):
         return out
 
     def extract_geometry(self, volumes, bound_min, bound_max, resolution, threshold, shard=None, sparse=None, sparse_mesh=None, attributes=None,
-                         views=None, simplify=None, texture=None, simplify_error=None):
+                         views=None, simplify=None, texture=None, simplify_error=None, topology=None):
         """-> vertices (V,3) float64, triangles (T,3) int32 as numpy arrays (implicit_surface.py:407-427).  The SDF lattice and
         the marching cubes both run on the device (the reference: 512 D2H copies + PyMCubes on the host); only the mesh is copied.
         sparse: sdf_grid's option of that name, with this call's threshold.  sparse_mesh (default: the attribute of that name, None = off):
@@ -1251,7 +1264,14 @@ class ImplicitSurface(nn.Module):
         compared in index coordinates (ops.mesh_distance with A = the extracted mesh, B = the simplified one; K36): the dict goes into
         self.last_simplify_stats["error"], in lattice spacings -- b_to_a.max bounds how far a simplified vertex is from the extracted surface,
         a_to_b what of that surface the simplified mesh lost.  Off: nothing is kept or launched and the stats have no such key.  ValueError
-        before any launch for another value, unknown or bad keywords, or when simplify is off.
+        before any launch for another value, unknown or bad keywords, or when simplify is off.  With "signed": True in the dict each
+        direction also holds signed_mean, inside and no_sign (K37): whether the simplification shrinks or inflates the surface.
+        topology (default: the attribute `mesh_topology`; None or False = off): True -> self.last_mesh_topology holds
+        ops.mesh_topology(...).report() of the mesh this call returns (K37: edges by class, closed / oriented / manifold / watertight, Euler
+        characteristic, genus, components, boundary loops, pinched vertices; area and volume in lattice spacings), taken on the
+        device-resident mesh after the simplification and before the read-back, on every route; with simplify also on,
+        self.last_simplify_stats["topology_before"] holds the report of the mesh before it.  Off: nothing is launched and
+        last_mesh_topology is None.  ValueError before any launch for another value.
         texture (default: the attribute `mesh_texture`; None, False or 0 = off): the tile edge in texels (3 to 64) or a dict of texture_mesh's
         keywords (texels, snap, max_move, chunk) -> a further result after the attribute dict (whose place holds None when only the
         texture is asked for): texture_mesh's dict for the returned mesh (K34), computed after marching cubes and
@@ -1261,11 +1281,13 @@ class ImplicitSurface(nn.Module):
         attributes = self._attribute_request(attributes, volumes, views)
         simplify = self._simplify_request(simplify)
         simplify_error = self._simplify_error_request(simplify_error, simplify)
+        topology = self._topology_request(topology)
         texture = self._texture_option(texture)
         if texture is not None:
             texture = {"threshold": threshold, **texture}
             self._texture_request(None, volumes, views, *(texture.get(k, d) for k, d in (("texels", 8), ("snap", 0), ("max_move", None))))
         self.last_simplify_stats = None
+        self.last_mesh_topology = None
         route, brick = self._lattice_route(sparse, sparse_mesh, shard)
         mesh = None
         if route == "mesh":
@@ -1283,10 +1305,15 @@ class ImplicitSurface(nn.Module):
         vertices, triangles = mesh
         if simplify is not None:
             full = (vertices, triangles) if simplify_error is not None else None
+            before = ops.mesh_topology(vertices, triangles).report() if topology else None
             vertices, triangles, _, self.last_simplify_stats = ops.simplify_mesh(vertices, triangles, simplify, origin=(-0.5, -0.5, -0.5))
+            if before is not None:
+                self.last_simplify_stats["topology_before"] = before
             if full is not None:
                 self.last_simplify_stats["error"] = ops.mesh_distance(*full, vertices, triangles, **simplify_error)
                 del full
+        if topology:
+            self.last_mesh_topology = ops.mesh_topology(vertices, triangles).report()
         b_max, b_min = bound_max.detach().cpu().numpy(), bound_min.detach().cpu().numpy()
         attrs = tex = None
         if attributes or texture is not None:          # on the device-resident vertices; span: the host expression's (float32) difference, widened
@@ -1305,7 +1332,7 @@ class ImplicitSurface(nn.Module):
     def validate(self, rays_o, rays_d, near, far, volumes, mask_volumes, imgs, features, match_features, intrs, c2ws, bound_min, bound_max,
                  hw, cos_anneal_ratio=1.0, step=None, extract_geometry=True, mesh_resolution=512, threshold=0.0, scene=None, shard=None, sparse=None,
                  sparse_mesh=None, mesh_attributes=None, surface_render=None, surface_fusion=None, mesh_simplify=None, mesh_texture=None,
-                 mesh_render=None, mesh_simplify_error=None):
+                 mesh_render=None, mesh_simplify_error=None, mesh_topology=None):
         """shard (gens_amd.distributed.Shard, optional): render only this rank's contiguous ray range and evaluate only its lattice
         chunks; the (P, 8) image buffer / the lattice slabs are gathered over RCCL, so every rank returns the whole image.  The jitter
         of EVERY ray is drawn on every rank from the identically seeded CPU generator (the reference's draw order) and sliced with
@@ -1321,7 +1348,8 @@ class ImplicitSurface(nn.Module):
         attributes are those of the simplified mesh (K33); self.last_simplify_stats holds its counts.  mesh_simplify_error: extract_geometry's
         `simplify_error` (True or a dict of ops.mesh_distance's keywords; default: the attribute of that name, None / False = off): the
         simplified mesh is measured against the extracted one (K36) into self.last_simplify_stats["error"]; ValueError before any launch
-        when the simplification is off.  mesh_texture: extract_geometry's
+        when the simplification is off.  mesh_topology: extract_geometry's `topology` (True; default: the attribute of that name, None /
+        False = off): self.last_mesh_topology holds the topology report of the returned mesh (K37).  mesh_texture: extract_geometry's
         `texture` with this scene's views (the tile edge in texels or a dict of texture_mesh's keywords; default: the attribute of that name,
         None / False / 0 = off) -> outputs["texture"], ["texture_seen"], ["texture_uv"] (K34), which save_validation_outputs writes as an
         OBJ beside the PLY.  mesh_render (default: the attribute of that name, None / False = off; True, or a dict of render_mesh's keywords
@@ -1341,6 +1369,7 @@ class ImplicitSurface(nn.Module):
                 raise ValueError("mesh_render: smooth shading needs mesh_attributes with \"normals\"")
         mesh_simplify = self._simplify_request(mesh_simplify) if extract_geometry else None      # (refused before anything is launched)
         mesh_simplify_error = self._simplify_error_request(mesh_simplify_error, mesh_simplify) if extract_geometry else None
+        mesh_topology = self._topology_request(mesh_topology) if extract_geometry else False
         mesh_texture = self._texture_option(mesh_texture) if extract_geometry else None
         surface_fusion = self.surface_fusion if surface_fusion is None else surface_fusion
         if surface_fusion:
@@ -1374,7 +1403,7 @@ class ImplicitSurface(nn.Module):
             mesh = self.extract_geometry(scene.volumes_nograd(), bound_min, bound_max, mesh_resolution, threshold, shard=shard, sparse=sparse,
                                          sparse_mesh=sparse_mesh, attributes=mesh_attributes, views=scene.views,
                                          simplify=0 if mesh_simplify is None else mesh_simplify, texture=0 if mesh_texture is None else mesh_texture,
-                                         simplify_error=False if mesh_simplify_error is None else mesh_simplify_error)
+                                         simplify_error=False if mesh_simplify_error is None else mesh_simplify_error, topology=mesh_topology)
             outputs["vertices"], outputs["triangles"] = mesh[0], mesh[1]
             for name, values in ((mesh[2] or {}) if len(mesh) >= 3 else {}).items():
                 outputs["vertex_" + name] = values

@@ -11,7 +11,7 @@ from .points import sample_mesh_points
 
 _f64, _i32, _u8 = torch.float64, torch.int32, torch.uint8
 MESH_DISTANCE_SAMPLES = 1_000_000
-MESH_DISTANCE_KEYS = ("density", "samples", "max_dist")        # what extract_geometry(simplify_error=dict) may name
+MESH_DISTANCE_KEYS = ("density", "samples", "max_dist", "signed")      # what extract_geometry(simplify_error=dict) may name
 NO_REGION = 255                                                # the region code of a query without a face
 
 distance_section_hook = None         # a callable(name), called where a part of mesh_distance begins (scripts/mesh_distance_bench.py records HIP events there)
@@ -122,8 +122,21 @@ def _direction_dict(n, figures):
     return out
 
 
-def mesh_distance_request(who, density=None, samples=MESH_DISTANCE_SAMPLES, max_dist=float("inf")):
+def _signed_figures(dist2, signed):
+    """(3,) float64 on the device over the matched samples (finite dist2): the sum of the signed distances that have a sign, the count of
+    negative ones, the count without a sign (NaN)."""
+    if dist2.shape[0] == 0:
+        return torch.zeros(3, device=dist2.device, dtype=_f64)
+    matched = torch.isfinite(dist2)
+    none = torch.isnan(signed)
+    return torch.stack([torch.where(matched & ~none, signed, torch.zeros_like(signed)).sum(), (matched & (signed < 0.0)).sum().to(_f64),
+                        (matched & none).sum().to(_f64)])
+
+
+def mesh_distance_request(who, density=None, samples=MESH_DISTANCE_SAMPLES, max_dist=float("inf"), signed=False):
     """The comparison's keywords, checked on the host -> (density or None, samples, max_dist)."""
+    if not isinstance(signed, bool):
+        raise ValueError(f"{who}: signed = {signed!r}: True or False")
     if density is not None:
         try:
             density = float("nan") if isinstance(density, bool) else float(density)
@@ -136,7 +149,7 @@ def mesh_distance_request(who, density=None, samples=MESH_DISTANCE_SAMPLES, max_
     return density, samples, distance_cap(who, max_dist)
 
 
-def mesh_distance(va, ta, vb, tb, density=None, samples=MESH_DISTANCE_SAMPLES, max_dist=float("inf"), return_samples=False):
+def mesh_distance(va, ta, vb, tb, density=None, samples=MESH_DISTANCE_SAMPLES, max_dist=float("inf"), return_samples=False, signed=False):
     """The two-sided distance between the meshes A = (va, ta) and B = (vb, tb): vertices (V, 3) float64 and triangles (T, 3) int32 on the
     device.  Each mesh is sampled with ops.sample_mesh_points -- ALL its vertices, then K24's lattice points at spacing `density` (the DTU
     score's sampler; the vertices come on top of the area-uniform lattice, so regions of small triangles weigh more: on a mesh whose
@@ -148,8 +161,12 @@ def mesh_distance(va, ta, vb, tb, density=None, samples=MESH_DISTANCE_SAMPLES, m
     here and left out of the rest), mean, rms, max, q50, q90, q99 (order statistics at index (p m) // 100 of the m matched distances);
     NaN where m = 0.  Python numbers: the sums are float64 on the device and the figures come back in one read (building the grids and
     sampling read sizes and extents back as they always do, and density = None reads the two areas).  return_samples: also
-    "samples_a", "dist_a", "face_a" (and _b): the device tensors behind the figures.  Unsigned, and one-sided figures differ: a hole in B
-    shows in a_to_b only.  ValueError before any launch for what closest_point_on_mesh, build_mesh_grid's inputs and the keywords exclude."""
+    "samples_a", "dist_a", "face_a" (and _b): the device tensors behind the figures.  One-sided figures differ: a hole in B
+    shows in a_to_b only.  signed=True (K37; off: not one more launch or key): each sample's distance also gets the sign that the OTHER mesh's
+    orientation gives it (ops.signed_distance_to_mesh: positive on the side its face normals point to) and a direction gains signed_mean
+    (the mean over the matched samples that have a sign; NaN if none has), inside (the count of negative ones) and no_sign (matched samples
+    whose closest point has no sign: on a boundary, flipped or non-manifold edge, a pinched vertex, a degenerate face); with return_samples
+    also "signed_a" / "signed_b".  ValueError before any launch for what closest_point_on_mesh, build_mesh_grid's inputs and the keywords exclude."""
     who = "mesh_distance"
     for name, t, dtype in (("va", va, _f64), ("ta", ta, _i32), ("vb", vb, _f64), ("tb", tb, _i32)):
         if not torch.is_tensor(t) or not t.is_cuda:
@@ -158,7 +175,7 @@ def mesh_distance(va, ta, vb, tb, density=None, samples=MESH_DISTANCE_SAMPLES, m
             raise ValueError(f"{who}: {name} is {tuple(t.shape)} {t.dtype}, expected (n, 3) {dtype}")
         if t.device != va.device:
             raise ValueError(f"{who}: va on {va.device}, {name} on {t.device}")
-    density, samples, cap = mesh_distance_request(who, density, samples, max_dist)
+    density, samples, cap = mesh_distance_request(who, density, samples, max_dist, signed)
     _distance_section("grids")
     meshes = [(_c(va.detach()), _c(ta.detach())), (_c(vb.detach()), _c(tb.detach()))]
     grids = [build_mesh_grid(v, t) for v, t in meshes]
@@ -174,17 +191,31 @@ def mesh_distance(va, ta, vb, tb, density=None, samples=MESH_DISTANCE_SAMPLES, m
     results = []
     for k in (0, 1):
         _distance_section("query_a_to_b" if k == 0 else "query_b_to_a")
-        results.append(mesh_closest_dist2(points[k], grids[1 - k], cap))
+        results.append(mesh_closest_dist2(points[k], grids[1 - k], cap, signed, signed))
+    signs = None
+    if signed:
+        from .mesh_topology import distance_sign, mesh_topology
+        _distance_section("sign")
+        signs = [distance_sign(points[k], *results[k], mesh_topology(*meshes[1 - k], normals=True)) for k in (0, 1)]
     _distance_section("reduce")
-    figures = torch.stack([_direction_figures(r[0]) for r in results]).cpu().tolist()
+    figures = [_direction_figures(r[0]) for r in results]
+    if signed:
+        figures = [torch.cat([f, _signed_figures(r[0], s)]) for f, r, s in zip(figures, results, signs)]
+    figures = torch.stack(figures).cpu().tolist()
     _distance_section("end")
     sides = [_direction_dict(points[k].shape[0], figures[k]) for k in (0, 1)]
+    if signed:
+        for side, f in zip(sides, figures):
+            with_sign = int(f[0]) - int(f[9])
+            side.update(signed_mean=f[7] / with_sign if with_sign else float("nan"), inside=int(f[8]), no_sign=int(f[9]))
     ha, hb = sides[0]["max"], sides[1]["max"]
     out = {"a_to_b": sides[0], "b_to_a": sides[1], "hausdorff": float("nan") if ha != ha or hb != hb else max(ha, hb),
            "chamfer": 0.5 * (sides[0]["mean"] + sides[1]["mean"]), "density_a": densities[0], "density_b": densities[1]}
     if return_samples:
         for k, s in enumerate("ab"):
             out["samples_" + s], out["dist_" + s], out["face_" + s] = points[k], torch.sqrt(results[k][0]), results[k][1]
+            if signed:
+                out["signed_" + s] = signs[k]
     return out
 
 

@@ -66,7 +66,8 @@ const char* gens_last_error(void);
  *       and K30's gens_vertex_points, gens_vertex_pack, and K31's gens_trace_begin, gens_trace_march, gens_trace_refine, gens_trace_gather,
  *       gens_surface_pack, and K32's gens_fuse_depth_maps, gens_fused_points, and K33's gens_cluster_keys, gens_cluster_triangles,
  *       gens_cluster_solve, and K34's gens_texture_points, gens_texture_snap, gens_texture_keep_better,
- *       gens_texture_pack, gens_texture_uv, and K35's gens_mesh_shade, and K36's gens_mesh_closest_point. */
+ *       gens_texture_pack, gens_texture_uv, and K35's gens_mesh_shade, and K36's gens_mesh_closest_point, and K37's gens_mesh_edge_keys,
+ *       gens_mesh_edge_classify, gens_mesh_fan_pairs, gens_mesh_vertex_classify, gens_mesh_pseudonormals, gens_mesh_distance_sign. */
 int gens_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -1322,6 +1323,80 @@ int gens_mesh_shade(const gens_mesh_shade_args* args, void* stream);
  * ---------------------------------------------------------------------------------------------------------- */
 int gens_mesh_closest_point(const gens_mesh_grid* grid, const double* queries, int64_t n_queries, double max_dist, double* dist2,
                             int32_t* face, double* point /* (n, 3) or NULL */, uint8_t* region /* or NULL */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * K37  The undirected edge table of a triangle mesh, its topology, Baerentzen-Aanaes pseudonormals and the sign of K36's distance
+ *      (ops.mesh_topology, ops.signed_distance_to_mesh, ops.mesh_distance(signed=True), io.mesh_report, python -m gens_amd.mesh_report,
+ *      ImplicitSurface.extract_geometry(topology=)), csrc/k37_mesh_topology.hip.  tests/mesh_topology_reference.py restates all of it in
+ *      numpy with dicts and loops.  vertices (V, 3) float64, triangles (T, 3) int32; V < 2^31 and 3 T < 2^31.
+ *
+ *   Definitions.
+ *     A face is VALID when its three indices lie in [0, V) and are pairwise distinct.  Other faces are counted and take part in nothing
+ *       else.  A valid face of zero area takes part in the topology and contributes a zero normal.
+ *     Half-edge h = 3 t + k runs from t[k] to t[(k + 1) % 3].  An EDGE is the unordered pair (lo, hi) of a valid face's half-edge; its id is
+ *       its rank in ascending (lo, hi); its key is (lo << 32) | hi.  A CORNER is (t, k), id 3 t + k, at vertex t[k].
+ *     The USES of an edge are its half-edges in ascending h -- what a stable sort of the keys leaves; the order is part of the rule.
+ *     Edge class: 1 boundary (one use), 2 manifold (two uses, one lo -> hi and one hi -> lo), 3 flipped (two uses in the same direction),
+ *       4 non-manifold (three or more uses).
+ *     FANS.  For every edge of class 2 or 3 and each of its two endpoints v, the corners that the edge's two faces have at v are joined.
+ *       The fans of a vertex are the resulting classes of its corners; a class is named by its smallest corner id.
+ *     Vertex flag byte: bit 0 referenced (by a valid face), bit 1 on a class-1 edge, bit 2 on a class-4 edge, bit 3 on a class-3 edge,
+ *       bit 4 fans > 1 (a pinch).  A vertex is MANIFOLD when bit 0 is set and bits 2 and 4 are clear.
+ *     Normals, float64, every operation rounded on its own, dot(u, v) = (u_x v_x + u_y v_y) + u_z v_z, cross as in K36:
+ *       face: c = (b - a) x (c - a), l = sqrt(dot(c, c)); c / l per component where l > 0 and finite, else (0, 0, 0); (0, 0, 0) for a face
+ *         that is not valid.
+ *       edge: the sum of the face normals of its uses, in ascending h, starting from 0, per component.
+ *       vertex: over its corners in ascending corner id, starting from 0: sum + angle * n_face per component, with u, v the edge vectors
+ *         from the corner's vertex to the face's next and previous vertex, angle = atan2(sqrt(dot(u x v, u x v)), dot(u, v)); a corner
+ *         whose angle is not finite is left out.  Neither sum is normalised.
+ *     The sign of a K36 result (dist2, face, point, region) for the query q:  NaN unless face is in [0, T) and dist2 is finite and >= 0;
+ *       +0 where dist2 == 0; otherwise n = the face normal (region 0), the vertex normal of t[face][region - 1] (regions 1 - 3; none if that
+ *       vertex has any of the flag bits 1 - 4), the edge normal of edge_of_halfedge[3 face + region - 4] (regions 4 - 6; none unless that
+ *       edge has class 2); s = dot(q - point, n); the result is sqrt(dist2) if s > 0, -sqrt(dist2) if s < 0, NaN where there is no n (region
+ *       7 and 255 included) or s is 0 or NaN.  Positive is the side the face normals point to: the sign follows the mesh's own orientation.
+ *       For a closed, oriented, manifold mesh the angle-weighted normal decides inside / outside exactly at every point of the surface
+ *       (Baerentzen and Aanaes, Signed distance computation using the angle weighted pseudonormal, 2005).
+ *
+ *   gens_mesh_edge_keys: per half-edge, key (3 T) int64 and forward (3 T) uint8 (1: the half-edge runs lo -> hi).  Half-edges of faces that
+ *     are not valid get the key INT64_MAX, which sorts last, and forward 0.
+ *   gens_mesh_edge_classify: per edge.  edge_key (E) int64: the distinct keys in ascending order without INT64_MAX; seg_start (E + 1) int32:
+ *     where each key's run begins in the sorted half-edges; order (3 T) int32: the half-edge ids in (stably) sorted order; forward: as
+ *     above, indexed by half-edge.  Writes edges (E, 2) int32 (lo, hi), edge_count (E), edge_forward (E) (uses that run lo -> hi),
+ *     edge_halfedges (E, 2) (the two smallest h, -1 where there is none), edge_class (E) uint8 and the inverse map edge_of_halfedge (3 T)
+ *     int32 (first filled with -1: what half-edges of faces that are not valid keep).  Entries of order outside [0, 3 T) and run bounds
+ *     outside [0, 3 T] are skipped / clamped, never read through.
+ *   gens_mesh_fan_pairs: per edge, pairs (2 E, 2) int32: rows 2 e and 2 e + 1 hold, for an edge of class 2 or 3, the corner ids that the
+ *     faces of its two smallest half-edges have at lo and at hi; (-1, -1) for other edges.  The rows go through gens_face_cc_hook /
+ *     gens_face_cc_compress with 3 T nodes (ids below zero are skipped there); a root is the smallest corner id.
+ *   gens_mesh_vertex_classify: per vertex.  corner_order (3 T') int32: the corner ids of valid faces stably sorted by their vertex (the
+ *     caller may pad it to 3 T entries; only [corner_start[0], corner_start[V]) is read); corner_start (V + 1) int32; corner_label (3 T) from
+ *     the compress launch.  Writes valence (V) int32, fans (V) int32 (the number of corners of the vertex that are their own label) and
+ *     flags (V) uint8.  n_halfedges is 3 T; ids outside their ranges are skipped.
+ *   gens_mesh_pseudonormals: three launches -- faces, then edges and vertices, which read the face normals.  face_normal (T, 3),
+ *     edge_normal (E, 3), vertex_normal (V, 3) float64.  One thread walks one segment in order: no atomics, deterministic.
+ *   gens_mesh_distance_sign: per query, signed (n) float64 by the rule above.  queries (n, 3), dist2 (n), face (n), point (n, 3),
+ *     region (n) as gens_mesh_closest_point wrote them.
+ *   Arguments are checked before any launch.  GENS_EINVAL: a negative count; more edges than half-edges; a half-edge count that is no
+ *     multiple of 3; a null pointer that the given counts would have the launch read or write.  GENS_ELIMIT: V, 3 T or n_queries >= 2^31.
+ *     Counts of zero succeed without the launch they would size.  The ABI version stays 12: no existing entry changes.
+ * ---------------------------------------------------------------------------------------------------------- */
+int gens_mesh_edge_keys(const int32_t* triangles, int64_t n_faces, int64_t n_vertices, int64_t* key, uint8_t* forward, void* stream);
+int gens_mesh_edge_classify(const int64_t* edge_key, const int32_t* seg_start, const int32_t* order, const uint8_t* forward, int64_t n_edges,
+                            int64_t n_halfedges, int32_t* edges, int32_t* edge_count, int32_t* edge_forward, int32_t* edge_halfedges,
+                            uint8_t* edge_class, int32_t* edge_of_halfedge, void* stream);
+int gens_mesh_fan_pairs(const int32_t* triangles, int64_t n_faces, const int32_t* edges, const int32_t* edge_halfedges,
+                        const uint8_t* edge_class, int64_t n_edges, int32_t* pairs, void* stream);
+int gens_mesh_vertex_classify(const int32_t* corner_order, const int32_t* corner_start, const int32_t* corner_label,
+                              const int32_t* edge_of_halfedge, const uint8_t* edge_class, int64_t n_vertices, int64_t n_halfedges,
+                              int64_t n_edges, int32_t* valence, int32_t* fans, uint8_t* flags, void* stream);
+int gens_mesh_pseudonormals(const double* vertices, const int32_t* triangles, int64_t n_vertices, int64_t n_faces, int64_t n_edges,
+                            const int32_t* seg_start, const int32_t* order, const int32_t* corner_start, const int32_t* corner_order,
+                            double* face_normal, double* edge_normal, double* vertex_normal, void* stream);
+int gens_mesh_distance_sign(const double* queries, int64_t n_queries, const double* dist2, const int32_t* face, const double* point,
+                            const uint8_t* region, const int32_t* triangles, int64_t n_faces, int64_t n_vertices, int64_t n_edges,
+                            const double* face_normal, const double* edge_normal, const double* vertex_normal,
+                            const int32_t* edge_of_halfedge, const uint8_t* edge_class, const uint8_t* vertex_flags, double* signed_out,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K14  C (m x n) = A^T B for tall row-major operands A (k x m), B (k x n), k >> m, n: the weight-gradient product of the training
