@@ -13,11 +13,24 @@
 //     matrices, G_{l-1} = (W_l^T G_l) * softplus'(a_{l-1}), split the same way.  The weight stream (1 KB pieces: one term of the A operand
 //     of one output tile and one 16-deep K block) goes global -> LDS once per workgroup of four waves, by LDS-direct buffer loads into a
 //     ring of four 8 KB chunks filled three chunks ahead.
-//   * the value kernel is the forward half of the same code (GRAD = false) reading the forward prefix of the same stream: the two kernels
-//     issue the same MFMAs in the same order on the same operands, so they return the SAME float32 sdf for the same point.
+//   * the value kernel is the forward half of the same code (GRAD = false): every accumulator receives the same MFMAs in the same order on
+//     the same operands as in the gradient kernel, so the two return the SAME float32 sdf for the same point.  At five levels it reads the
+//     forward prefix of the gradient kernel's stream.
+//   * at three levels forward layer 3 reads seven hidden K blocks, not eight: its hidden inputs end at unit 100 (the skip connection fills
+//     the row), so the weights of block 7 (units 112..127) are zeros by construction and the stream leaves them out (GB_HID3) -- 24 MFMAs
+//     per wave, and with them layer 2's softplus and split of those sixteen units, which nothing reads any more.
 //   * at three levels the value kernel is built for TWO waves per SIMD (two workgroups per CU, each with its own ring): one wave's MFMAs
 //     issue while the other does its softplus and split, which a single wave between its sched_barrier fences cannot overlap.  That takes
 //     <= 256 registers without scratch (a spill would also count in the vmcnt of the chunk boundaries): see DIET in the kernel.
+//   * that kernel can also walk a forward layer TILE BY TILE (GENS_K6B_TILE_MAJOR=1, TM in the kernel; make k6b_tile_major): all K blocks
+//     of output tile t -- conditioning, at layer 3 the point encoding, hidden -- as ONE segment, softplus of acc[t] in place, then tile
+//     t + 1; the splits into H follow the fourth tile, because H is the operand of all four.  A wave then alternates four times per layer
+//     between ~72 MFMAs and a quarter of the vector work, instead of 288 MFMAs and one block of vector work, so that its partner on the SIMD
+//     finds more places to run the opposite phase.  Per accumulator the MFMAs, their operands and their order are unchanged, and so is every
+//     result bit.  The stream is the kernel's own (gens_amd.ops._pack_grad_pieces(order="tile"): [layer][tile][block][term], the layer
+//     offsets of the gradient stream); the conditioning blocks that wait in LDS come back once per tile and x is encoded again once per
+//     tile at layer 3 (96 + 64 registers for H and acc stay, as does the LDS).  NOT the shipped order: measured against block-major it
+//     did not move the step by the project's rule (profiles/r29_sdf_value_tile_major.txt).
 //   * softplus and softplus' (float32), the trilinear look-up and its Jacobians, the stash of layer 2's softplus' and the chain rule to x
 //     are k6gh's; the gradients need no scaling (bf16 has float32's range).
 #include "common.h"
@@ -57,6 +70,26 @@ typedef float f32x4v __attribute__((ext_vector_type(4)));
 #endif
 // The five-level gradient kernel keeps placement 0: it holds 508 of 512 registers, and with the refill between its MFMAs it spills.
 #define GB_PLACE(NLEV_, GRAD_) ((GRAD_) && (NLEV_) == 5 ? 0 : GENS_K6B_PLACE)
+
+// The order in which a forward layer of the two-wave value kernel walks its products (GB_TILE_MAJOR, TM in the kernel):
+//   0  block by block, all four tiles per K block and one softplus of all 64 accumulators per layer, on the forward prefix of the gradient
+//      stream (the order of every other instantiation, and the shipped one)
+//   1  tile by tile: all K blocks of output tile t, its softplus, then tile t + 1 -- four short matrix / vector alternations per layer, on a
+//      value-only stream packed [layer][tile][block][term].  Built, measured and NOT shipped: the step did not move by the project's rule
+//      (profiles/r29_sdf_value_tile_major.txt); kept for that A/B: make -C gens_amd/csrc k6b_tile_major
+// Every accumulator receives the same MFMAs on the same operands in the same order in both, and so every result bit is the same.
+#ifndef GENS_K6B_TILE_MAJOR
+#define GENS_K6B_TILE_MAJOR 0
+#endif
+#define GB_TILE_MAJOR(NLEV_, GRAD_) (GENS_K6B_TILE_MAJOR && GB_OCC(NLEV_, GRAD_) == 2)
+// Hidden K blocks that forward layer 3 reads.  Its hidden inputs end at unit 100 (the skip connection takes the rest of the row), so block 7
+// (units 112..127) multiplies weights that are zero by construction: seven blocks at three levels, in both kernels.  8 rebuilds the stream with
+// that block for the A/B.  The five-level kernels keep all eight: their gradient kernel holds 508 of 512 registers, and without the block its
+// register allocation comes out with 12 bytes of scratch per lane (the two five-level kernels share one stream).
+#ifndef GENS_K6B_HID3
+#define GENS_K6B_HID3 7
+#endif
+#define GB_HID3(NLEV_) ((NLEV_) == 3 ? GENS_K6B_HID3 : 8)
 
 // Cycle stamps of the gradient kernel's phases (build with -DGENS_K6B_STAMPS: make -C gens_amd/csrc stamps; scripts/probe/k6b_stamps_probe.py
 // reads them): never in the shipped library.  GB_STAMP(K_) ends a stretch of kind K_: 0 products (MFMAs, their LDS reads, whatever sits in
@@ -168,7 +201,9 @@ __device__ __forceinline__ float4 sample_volume4b(const float4* __restrict__ v, 
 }
 
 // The piece stream, in the order the kernels consume it (gens_amd.ops._pack_grad_pieces(..., terms=3)): k6gh's order with three pieces
-// (x0, x1, x2) per (K block, output tile) instead of (hi, lo).  The value kernel reads the forward part only.
+// (x0, x1, x2) per (K block, output tile) instead of (hi, lo), and forward layer 3 with GB_HID3 hidden blocks.  The block-major value kernels
+// read the forward part only; the tile-major one reads a stream of its own (order="tile"): the same pieces, the same layer offsets fwd(l),
+// [tile][block][term] within a layer.
 template <int NLEV>
 struct GradShapeB {
     static constexpr int CF = 4 * NLEV;
@@ -176,8 +211,10 @@ struct GradShapeB {
     static constexpr int NC = (5 * NCH + 1 + 7) / 8;       // conditioning K blocks: 5 encodings per channel + the constant-one slot
     static constexpr int TC = (5 * NCH + 15) / 16;         // accumulator tiles of the conditioning gradient (16 slots of a half per tile)
     static constexpr int BLK = 4 * GB_TERMS;               // pieces of one forward K block
-    static constexpr int fwd(int l) { return l == 0 ? 0 : BLK * (2 + (l - 1) * (NC + 8) + (l > 3 ? 2 : 0)); }      // first piece of forward layer l
-    static constexpr int FWD_PIECES = fwd(5) + BLK * (NC + 8);
+    static constexpr int HID3 = GB_HID3(NLEV);            // hidden K blocks of forward layer 3
+    static constexpr int blocks(int l) { return l == 0 ? 2 : l == 3 ? NC + 2 + HID3 : NC + 8; }      // K blocks of forward layer l
+    static constexpr int fwd(int l) { return l == 0 ? 0 : BLK * (2 + (l - 1) * (NC + 8) + (l > 3 ? 2 + HID3 - 8 : 0)); }      // first piece of forward layer l
+    static constexpr int FWD_PIECES = fwd(5) + BLK * blocks(5);
     static constexpr int rev_tiles(int l) { return 4 + TC + (l == 3 ? 1 : 0); }
     static constexpr int rev_blocks(int l) { return l == 2 ? 7 : 8; }
     static constexpr int rev(int l) {      // first piece of reverse layer l = 5 .. 1; rev(0): the G_0 blocks
@@ -205,6 +242,8 @@ __global__ __launch_bounds__(64 * GB_WAVES, GB_OCC(NLEV, GRAD)) void sdf_bf16x3_
     constexpr bool DIET = GB_OCC(NLEV, GRAD) == 2;
     constexpr int GT = DIET ? 1 : GB_GT;
     constexpr int PLACE = GB_PLACE(NLEV, GRAD);
+    // TM: the forward layers tile by tile on the tile-major value stream (GB_TILE_MAJOR above)
+    constexpr bool TM = GB_TILE_MAJOR(NLEV, GRAD);
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -385,22 +424,46 @@ __global__ __launch_bounds__(64 * GB_WAVES, GB_OCC(NLEV, GRAD)) void sdf_bf16x3_
     // the six products of one operand pair, smallest first: weight term WA_ x activation term WB_
 #define GB_TERM(WA_, WB_, REV_, B_)                                                                      \
     _Pragma("unroll") for (int t_ = 0; t_ < GT; ++t_) if (t_ < nt_) {                                    \
-        if (REV_) GB_MFMA(GB_RACC(t0_ + t_), abuf[par][GB_TERMS * t_ + (WA_)], (B_)[i_].p[(WB_)])        \
-        else GB_MFMA(acc[(t0_ + t_) & 3], abuf[par][GB_TERMS * t_ + (WA_)], (B_)[i_].p[(WB_)])           \
+        if (REV_) GB_MFMA(GB_RACC(t0_ + t_), abuf[par][GB_TERMS * t_ + (WA_)], B_(i_).p[(WB_)])          \
+        else GB_MFMA(acc[(t0_ + t_) & 3], abuf[par][GB_TERMS * t_ + (WA_)], B_(i_).p[(WB_)])             \
     }
-    // CNT_ K blocks of NT_ output tiles from piece P0_ on, B operands B_[0 .. CNT_); REV_: the accumulators of a reverse block.  The A
-    // operands arrive in groups of GT tiles (three terms each), one group ahead of the MFMAs that read them.  Within a group the
-    // accumulators alternate.
-#define GB_SEGMENT(P0_, CNT_, NT_, B_, REV_)                                                             \
+    // the B operand of K block I_ of a segment: one of the kernel's three operand arrays, or (GB_OP_CPH) their concatenation as a tile-major
+    // forward layer l reads it -- layer 0 the point encoding, the others C, at layer 3 the point-encoding block in P[0] (GB_PREP_TM), then H
+    // (GB_OP_CPH and GB_PREP_TM expand inside the tile-major layer loop only and read its loop variable l and the kernel's lane, x, CL, NC)
+#define GB_OP_P(I_) P[I_]
+#define GB_OP_C(I_) C[I_]
+#define GB_OP_H(I_) H[I_]
+#define GB_OP_CPH(I_) (*(l == 0 ? &P[(I_) & 1] : (I_) < NC ? &C[(I_) < NC ? (I_) : 0] : l == 3 && (I_) < NC + 2 ? &P[0] : &H[((I_) - NC - (l == 3 ? 2 : 0)) & 7]))
+    // what a tile-major segment does in front of K block I_: at block 0 the conditioning blocks that wait in LDS come back, at layer 3's two
+    // point-encoding blocks x is encoded again (as the block-major two-wave build does once per layer, here once per tile)
+#define GB_PREP_NONE(I_)
+#define GB_PREP_TM(I_)                                                                                   \
+    if (l > 0 && (I_) == 0) {      /* (opaque lane: a new address to the compiler, or it keeps the blocks of the tile before) */ \
+        int lane_o = lane;                                                                               \
+        asm volatile("" : "+v"(lane_o));                                                                 \
+        _Pragma("unroll") for (int b_ = 0; b_ < GB_NCL; ++b_)                                            \
+            _Pragma("unroll") for (int k_ = 0; k_ < GB_TERMS; ++k_) C[NC - GB_NCL + b_].p[k_] = CL[(b_ * GB_TERMS + k_) * 64 + lane_o]; \
+    }                                                                                                    \
+    if (l == 3 && (I_) >= NC && (I_) < NC + 2) {      /* (opaque x, or the compiler keeps the first copy) */ \
+        _Pragma("unroll") for (int a_ = 0; a_ < 3; ++a_) asm volatile("" : "+v"(x[a_]));                 \
+        GB_ENCODE_POINT(P, (I_) - NC)                                                                    \
+    }
+    // CNT_ K blocks of NT_ output tiles TB_ .. TB_ + NT_ - 1 from piece P0_ on, B operands B_(0 .. CNT_ - 1), PREP_(i) in front of block i;
+    // REV_: the accumulators of a reverse block.  The A operands arrive in groups of GT tiles (three terms each), one group ahead of the
+    // MFMAs that read them.  Within a group the accumulators alternate.
+    // A tile base other than 0 goes with NT_ = 1 (one tile per segment: the tile-major calls); the offset of the next group's pieces counts
+    // tiles from 0 and does not know TB_.
+#define GB_SEGMENT(P0_, CNT_, NT_, TB_, B_, PREP_, REV_)                                                 \
     {                                                                                                    \
         constexpr int ng__ = ((NT_) + GT - 1) / GT;      /* (CNT_ and NT_ are constant expressions at every call) */ \
         GB_LOAD(par, (P0_), GB_TERMS * ((NT_) < GT ? (NT_) : GT))                                        \
         _Pragma("unroll") for (int q_ = 0; q_ < (CNT_) * ng__; ++q_) {                                   \
-            const int i_ = q_ / ng__, t0_ = (q_ % ng__) * GT, nt_ = (NT_) - t0_ < GT ? (NT_) - t0_ : GT; \
+            const int i_ = q_ / ng__, t0_ = (TB_) + (q_ % ng__) * GT, nt_ = (TB_) + (NT_) - t0_ < GT ? (TB_) + (NT_) - t0_ : GT; \
             if (q_ + 1 < (CNT_) * ng__) {                                                                \
                 const int i2_ = (q_ + 1) / ng__, t2_ = ((q_ + 1) % ng__) * GT, n2_ = (NT_) - t2_ < GT ? (NT_) - t2_ : GT; \
                 GB_LOAD(par ^ 1, (P0_) + GB_TERMS * ((NT_) * i2_ + t2_), GB_TERMS * n2_)                  \
             }                                                                                            \
+            PREP_(i_)                                                                                    \
             __builtin_amdgcn_sched_barrier(0);                                                           \
             GB_TERM(2, 0, REV_, B_) GB_TERM(1, 1, REV_, B_) GB_TERM(0, 2, REV_, B_)                      \
             GB_TERM(1, 0, REV_, B_) GB_TERM(0, 1, REV_, B_) GB_TERM(0, 0, REV_, B_)                      \
@@ -429,76 +492,110 @@ __global__ __launch_bounds__(64 * GB_WAVES, GB_OCC(NLEV, GRAD)) void sdf_bf16x3_
 
     // ------------------------------------------------------------------ forward
     float s_val = s_cond;
-    GB_ZERO();
-    GB_SEGMENT(S::fwd(0), 2, 4, P, false);
+    if constexpr (TM) {
+        // tile by tile: the matrix pipe has tile t + 1 of this wave, or whatever the other wave of the SIMD is at, while softplus runs on
+        // tile t; the splits wait for the fourth tile, because H is the operand of all four
 #pragma unroll
-    for (int l = 0; l < 6; ++l) {
-        if (l > 0) {
-            GB_ZERO();
-            if constexpr (DIET) {      // (opaque lane: a new address to the compiler, or it keeps the blocks of the layer before)
-                int lane_o = lane;
-                asm volatile("" : "+v"(lane_o));
+        for (int l = 0; l < 6; ++l) {
 #pragma unroll
-                for (int b = 0; b < GB_NCL; ++b)
+            for (int t = 0; t < 4; ++t) {
 #pragma unroll
-                    for (int k = 0; k < GB_TERMS; ++k) C[NC - GB_NCL + b].p[k] = CL[(b * GB_TERMS + k) * 64 + lane_o];
-            }
-            GB_SEGMENT(S::fwd(l), NC, 4, C, false);
-            if (l == 3) {
-                if constexpr (!DIET) {
-                    GB_SEGMENT(S::fwd(3) + S::BLK * NC, 2, 4, P, false);
+                for (int r = 0; r < 16; ++r) acc[t][r] = 0.0f;
+                if (l == 0) {
+                    GB_SEGMENT(S::fwd(0) + GB_TERMS * 2 * t, 2, 1, t, GB_OP_CPH, GB_PREP_TM, false);
+                } else if (l == 3) {
+                    GB_SEGMENT(S::fwd(3) + GB_TERMS * (NC + 2 + S::HID3) * t, NC + 2 + S::HID3, 1, t, GB_OP_CPH, GB_PREP_TM, false);
                 } else {
-                    // x is encoded again, one K block at a time (the same instructions on the same x: the same bits), instead of 24 registers
-                    // held from the prologue to here; opaque, or the compiler keeps the first copy
+                    GB_SEGMENT(S::fwd(l) + GB_TERMS * (NC + 8) * t, NC + 8, 1, t, GB_OP_CPH, GB_PREP_TM, false);
+                }
+                GB_STAMP(0)
+                f32x16 d;
+                GB_SOFTPLUS_TILE(acc[t], acc[t], d);
+                GB_STAMP(4)
+            }
 #pragma unroll
-                    for (int pb = 0; pb < 2; ++pb) {
+            for (int t = 0; t < 4; ++t) {
+                if (l < 5) {
+                    GB_SPLIT_TILE(t, acc[t]);
+                } else {    // layer 6 is one row: the value is a dot product
 #pragma unroll
-                        for (int a = 0; a < 3; ++a) asm volatile("" : "+v"(x[a]));
-                        GB_ENCODE_POINT(P, pb)
-                        GB_SEGMENT(S::fwd(3) + S::BLK * (NC + pb), 1, 4, P, false);
+                    for (int r = 0; r < 16; ++r) s_val = __builtin_fmaf(acc[t][r], wo[16 * t + r], s_val);
+                }
+            }
+            GB_STAMP(4)
+        }
+    } else {
+        GB_ZERO();
+        GB_SEGMENT(S::fwd(0), 2, 4, 0, GB_OP_P, GB_PREP_NONE, false);
+#pragma unroll
+        for (int l = 0; l < 6; ++l) {
+            if (l > 0) {
+                GB_ZERO();
+                if constexpr (DIET) {      // (opaque lane: a new address to the compiler, or it keeps the blocks of the layer before)
+                    int lane_o = lane;
+                    asm volatile("" : "+v"(lane_o));
+#pragma unroll
+                    for (int b = 0; b < GB_NCL; ++b)
+#pragma unroll
+                        for (int k = 0; k < GB_TERMS; ++k) C[NC - GB_NCL + b].p[k] = CL[(b * GB_TERMS + k) * 64 + lane_o];
+                }
+                GB_SEGMENT(S::fwd(l), NC, 4, 0, GB_OP_C, GB_PREP_NONE, false);
+                if (l == 3) {
+                    if constexpr (!DIET) {
+                        GB_SEGMENT(S::fwd(3) + S::BLK * NC, 2, 4, 0, GB_OP_P, GB_PREP_NONE, false);
+                    } else {
+                        // x is encoded again, one K block at a time (the same instructions on the same x: the same bits), instead of 24 registers
+                        // held from the prologue to here; opaque, or the compiler keeps the first copy
+#pragma unroll
+                        for (int pb = 0; pb < 2; ++pb) {
+#pragma unroll
+                            for (int a = 0; a < 3; ++a) asm volatile("" : "+v"(x[a]));
+                            GB_ENCODE_POINT(P, pb)
+                            GB_SEGMENT(S::fwd(3) + S::BLK * (NC + pb), 1, 4, 0, GB_OP_P, GB_PREP_NONE, false);
+                        }
                     }
                 }
+                GB_SEGMENT(S::fwd(l) + S::BLK * (NC + (l == 3 ? 2 : 0)), (l == 3 ? S::HID3 : 8), 4, 0, GB_OP_H, GB_PREP_NONE, false);
             }
-            GB_SEGMENT(S::fwd(l) + S::BLK * (NC + (l == 3 ? 2 : 0)), 8, 4, H, false);
+            GB_STAMP(0)
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                f32x16 h, d;
+                if (l == 3) {
+                    GB_SOFTPLUS_TILE(acc[t], h, D3[t]);
+                } else if (l == 4) {
+                    GB_SOFTPLUS_TILE(acc[t], h, D4[t]);
+                } else {
+                    GB_SOFTPLUS_TILE(acc[t], h, d);
+                }
+                if constexpr (GRAD) {
+                    if (l < 2) {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) DS[(l * 16 + 4 * t + q) * 64 + lane] = make_float4(d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]);
+                    }
+                    if (l == 2) {
+#pragma unroll
+                        for (int q = 0; q < 4; ++q)      // (the register's offset in the VECTOR offset: see k6g_sdf_grad.hip)
+                            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, (f32x4v){d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]}), stash,
+                                                                   stash_lane + (uint32_t)(4 * t + q) * 1024u, 0, 0);
+                        dirty = 1;
+                    }
+                }
+                if (l < 5) {
+                    GB_SPLIT_TILE(t, h);
+                } else {    // layer 6 is one row: the value is a dot product, and G_5 = w_last * softplus' starts the reverse pass
+                    f32x16 g;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const float w = wo[16 * t + r];                      // w_last / c in this lane's accumulator order
+                        s_val = __builtin_fmaf(h[r], w, s_val);
+                        if (GRAD) g[r] = (w * GB_C) * d[r];
+                    }
+                    if constexpr (GRAD) GB_SPLIT_TILE(t, g);
+                }
+            }
+            GB_STAMP(4)
         }
-        GB_STAMP(0)
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            f32x16 h, d;
-            if (l == 3) {
-                GB_SOFTPLUS_TILE(acc[t], h, D3[t]);
-            } else if (l == 4) {
-                GB_SOFTPLUS_TILE(acc[t], h, D4[t]);
-            } else {
-                GB_SOFTPLUS_TILE(acc[t], h, d);
-            }
-            if constexpr (GRAD) {
-                if (l < 2) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) DS[(l * 16 + 4 * t + q) * 64 + lane] = make_float4(d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]);
-                }
-                if (l == 2) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)      // (the register's offset in the VECTOR offset: see k6g_sdf_grad.hip)
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, (f32x4v){d[4 * q], d[4 * q + 1], d[4 * q + 2], d[4 * q + 3]}), stash,
-                                                               stash_lane + (uint32_t)(4 * t + q) * 1024u, 0, 0);
-                    dirty = 1;
-                }
-            }
-            if (l < 5) {
-                GB_SPLIT_TILE(t, h);
-            } else {    // layer 6 is one row: the value is a dot product, and G_5 = w_last * softplus' starts the reverse pass
-                f32x16 g;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float w = wo[16 * t + r];                      // w_last / c in this lane's accumulator order
-                    s_val = __builtin_fmaf(h[r], w, s_val);
-                    if (GRAD) g[r] = (w * GB_C) * d[r];
-                }
-                if constexpr (GRAD) GB_SPLIT_TILE(t, g);
-            }
-        }
-        GB_STAMP(4)
     }
     // not-a-number inputs must come out as not-a-number (the reference's layers propagate them; the max / median forms of the activation drop
     // them): a poison term 0 * (sum of the inputs), NaN iff one of them is NaN or infinite
@@ -535,11 +632,11 @@ __global__ __launch_bounds__(64 * GB_WAVES, GB_OCC(NLEV, GRAD)) void sdf_bf16x3_
                     }
             }
             if (l == 3) {
-                GB_SEGMENT(S::rev(3), 8, 4 + TC + 1, H, true);
+                GB_SEGMENT(S::rev(3), 8, 4 + TC + 1, 0, GB_OP_H, GB_PREP_NONE, true);
             } else if (l == 2) {
-                GB_SEGMENT(S::rev(2), 7, 4 + TC, H, true);
+                GB_SEGMENT(S::rev(2), 7, 4 + TC, 0, GB_OP_H, GB_PREP_NONE, true);
             } else {
-                GB_SEGMENT(S::rev(l), 8, 4 + TC, H, true);
+                GB_SEGMENT(S::rev(l), 8, 4 + TC, 0, GB_OP_H, GB_PREP_NONE, true);
             }
             // G_{l-1} = (W_l^T G_l) * softplus'(a_{l-1})
             GB_STAMP(0)
@@ -644,6 +741,12 @@ __global__ __launch_bounds__(64 * GB_WAVES, GB_OCC(NLEV, GRAD)) void sdf_bf16x3_
 #undef GB_MFMA
 #undef GB_RACC
 #undef GB_TERM
+#undef GB_OP_P
+#undef GB_OP_C
+#undef GB_OP_H
+#undef GB_OP_CPH
+#undef GB_PREP_NONE
+#undef GB_PREP_TM
 #undef GB_SEGMENT
 #undef GB_ZERO
 #undef GB_SOFTPLUS_TILE
@@ -656,7 +759,17 @@ extern "C" int gens_sdf_bf16x3_pieces(int n_levels) {
     return n_levels == 3 ? GradShapeB<3>::NCHUNK * GB_CH : n_levels == 5 ? GradShapeB<5>::NCHUNK * GB_CH : 0;
 }
 
-static GensLdsOptIn g_grad_lds3, g_grad_lds5;      // the gradient kernels' 160 KB of LDS, granted once per device
+// What the packer has to know about this build (the orders are compile-time switches: GENS_K6B_TILE_MAJOR, GENS_K6B_HID3).
+extern "C" int gens_sdf_bf16x3_layout(int n_levels, int out[3]) {
+    GENS_CHECK_ARG(n_levels == 3 || n_levels == 5, GENS_ELIMIT, "gens_sdf_bf16x3_layout: built for 3 or 5 volume levels, got %d", n_levels);
+    GENS_CHECK_ARG(out, GENS_EINVAL, "gens_sdf_bf16x3_layout: null output");
+    out[0] = (n_levels == 3 ? GradShapeB<3>::NCHUNK_FWD : GradShapeB<5>::NCHUNK_FWD) * GB_CH;
+    out[1] = n_levels == 3 ? GB_TILE_MAJOR(3, false) : GB_TILE_MAJOR(5, false);
+    out[2] = n_levels == 3 ? GB_HID3(3) : GB_HID3(5);
+    return 0;
+}
+
+static GensLdsOptIn g_grad_lds3, g_grad_lds5;     // the gradient kernels' 160 KB of LDS, granted once per device
 
 extern "C" int64_t gens_sdf_grad_f16_stash_bytes(void);      // the stash is k6gh's: the same slots, the same layout
 

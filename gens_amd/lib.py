@@ -152,6 +152,7 @@ SIGNATURES = {
     "gens_sdf_value_bf16x3": [_pp, _ip, _i, _p, _p, _f, _f, _p, _p, _l, _p, _p, _p],
     "gens_sdf_grad_bf16x3": [_pp, _ip, _i, _p, _p, _f, _f, _p, _p, _l, _p, _p, _p, _p, _p],
     "gens_sdf_bf16x3_pieces": [_i],
+    "gens_sdf_bf16x3_layout": [_i, _ip],
     "gens_sdf_bf16x3_residency": [_i, _i, _ip],
     "gens_lncc_fwd": [_p, _p, _l, _i, _i, _i, _p, _p, _p],
     "gens_lncc_bwd": [_p, _p, _p, _p, _l, _i, _i, _i, _p, _p, _p],

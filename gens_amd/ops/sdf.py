@@ -72,11 +72,21 @@ class SdfMlpPlan:
                 if not gvmax < 6.0e4:
                     self.grad_pieces = None
             # the three-term bfloat16 kernels (k6b, generation "bf16x3" of the "f32" arithmetic): 3 and 5 levels, no range limit
-            self.bf16x3_pieces = None
+            # The library says how its kernels walk the stream: how many hidden blocks layer 3 reads, and whether the value kernel reads the
+            # forward prefix of the gradient kernel's stream (the shipped build) or a tile-major stream of its own (make k6b_tile_major).
+            self.bf16x3_pieces = self.bf16x3_value_pieces = None
             n_pieces = L.load().gens_sdf_bf16x3_pieces(self.n_levels) if self.n_levels in (3, 5) else 0
             if n_pieces:
-                self.bf16x3_pieces, _ = _pack_grad_pieces(ws, bs, self.n_levels, n_pieces, terms=3)
+                layout = (C.c_int * 3)()
+                if L.load().gens_sdf_bf16x3_layout(self.n_levels, layout) != 0:
+                    raise RuntimeError(L.load().gens_last_error().decode())
+                n_value, tile_major, hid3 = layout
+                self.bf16x3_pieces, _ = _pack_grad_pieces(ws, bs, self.n_levels, n_pieces, terms=3, hid3=hid3)
                 assert self.bf16x3_pieces.shape[0] == n_pieces
+                self.bf16x3_value_pieces = self.bf16x3_pieces
+                if tile_major:
+                    self.bf16x3_value_pieces, _ = _pack_grad_pieces(ws, bs, self.n_levels, n_value, terms=3, hid3=hid3, order="tile")
+                    assert self.bf16x3_value_pieces.shape[0] == n_value
             self.overflow = torch.zeros(1, device=dev, dtype=torch.int32)
         self.wf_table, self.wb_table, self.bias_table = L.ptr_table(self.wf), L.ptr_table(self.wb), L.ptr_table(self.bias)
         self.key = SdfMlpPlan.version(net)
@@ -96,7 +106,7 @@ _SDF_STREAMS = {
     "gens_sdf_grad_bf16x3": ("bf16x3_pieces", torch.bfloat16, "grad_row", False, sdf_grad_f16_stash, False),
     "gens_sdf_grad": ("grad_stream", _f32, "grad_row", False, sdf_grad_stash, False),
     "gens_sdf_value_f16": ("value_units", torch.float16, "value_w_out", False, None, True),
-    "gens_sdf_value_bf16x3": ("bf16x3_pieces", torch.bfloat16, "grad_row", False, None, False),
+    "gens_sdf_value_bf16x3": ("bf16x3_value_pieces", torch.bfloat16, "grad_row", False, None, False),
     "gens_sdf_value": ("value_stream", _f32, "value_row", False, None, False),
 }
 

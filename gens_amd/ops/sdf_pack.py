@@ -119,20 +119,23 @@ def _forward_layers(ws, bs):
         yield h, skip, torch.cat([_C * w[:, 128:], _C * b, zero], 1)
 
 
-def _forward_blocks(ws, bs, tables, order, hid3=None):
+def _forward_blocks(ws, bs, tables, parts, hid3=None, order="block"):
     """The forward half of a stream as a list of _gather results: layer 0's point-encoding blocks, then per layer 1..5 its "hid", "skip"
-    (layer 3 only) and "cond" blocks in the given order.  hid3: how many hidden blocks layer 3 reads (default: all)."""
+    (layer 3 only) and "cond" blocks in the sequence `parts`.  hid3: how many hidden blocks layer 3 reads (default: all).
+    order: "block" -- every entry [block][tile]; "tile" -- one entry per layer, [tile][block] over all of the layer's blocks."""
+    assert order in ("block", "tile")
     hid, pe, cond = tables
     pe_skip = torch.where(pe == -1, torch.full_like(pe, -2), pe)                  # the one slot of the point encoding carries nothing at the skip
     out = []
     for l, (h, skip, rest) in enumerate(_forward_layers(ws, bs)):
         if l == 0:
-            out.append(_gather(rest, pe))
-            continue
-        part = {"hid": _gather(h, hid[:hid3] if l == 3 else hid), "cond": _gather(rest, cond)}
-        if l == 3:
-            part["skip"] = _gather(skip, pe_skip)
-        out += [part[name] for name in order if name in part]
+            layer = [_gather(rest, pe)]
+        else:
+            part = {"hid": _gather(h, hid[:hid3] if l == 3 else hid), "cond": _gather(rest, cond)}
+            if l == 3:
+                part["skip"] = _gather(skip, pe_skip)
+            layer = [part[name] for name in parts if name in part]
+        out += layer if order == "block" else [torch.cat(layer, 0).transpose(0, 1)]
     return out
 
 
@@ -238,7 +241,7 @@ def _pack_value_units(ws, bs, n_levels):
     return stream, _output_row(ws[6][0], tables[2], 8 * tables[2].shape[0]), float(units.abs().max())
 
 
-def _pack_grad_pieces(ws, bs, n_levels, n_pieces=None, terms=2):
+def _pack_grad_pieces(ws, bs, n_levels, n_pieces=None, terms=2, hid3=None, order="block"):
     """The piece stream of gens_sdf_grad_f16 (k6gh_sdf_grad_f16.hip): 1 KB pieces = the A operand (hi or lo halfs) of one 32-row output
     tile and one 16-deep K block, lane (m, kh) holding row m's weights for the eight reduction slots of lane half kh (_value_slots).
     Forward: layer 0's two point-encoding K blocks, then per layer the conditioning K blocks, (layer 3: the point-encoding blocks,) the
@@ -247,11 +250,17 @@ def _pack_grad_pieces(ws, bs, n_levels, n_pieces=None, terms=2):
     point-encoding tile, rows ordered as in _pack_grad_stream; then the eight blocks of G_0 for the point-encoding tile.  Padded with
     zeros to whole chunks of eight pieces.  -> (pieces (N, 64, 8) float16, largest magnitude handed to half precision).
     terms=3: the stream of gens_sdf_value_bf16x3 / gens_sdf_grad_bf16x3 (k6b_sdf_bf16x3.hip) -- the same order with three round-to-nearest
-    bfloat16 terms (x0, x1, x2) per (block, tile) instead of (hi, lo): -> (pieces (N, 64, 8) bfloat16, largest magnitude)."""
+    bfloat16 terms (x0, x1, x2) per (block, tile) instead of (hi, lo): -> (pieces (N, 64, 8) bfloat16, largest magnitude).
+    hid3: how many hidden K blocks forward layer 3 keeps (default: all eight).  The layer's hidden inputs end at unit 100, so block 7 (units
+    112..127) is zeros by construction (_forward_layers); the bf16x3 kernels read seven (SdfMlpPlan asks the library), the split-half
+    kernel reads all eight.
+    order="tile": the value-only stream of the two-wave gens_sdf_value_bf16x3 kernel -- the forward pieces alone, the same bytes, within
+    every layer [tile][block][term] instead of [block][tile][term], so that the kernel can finish (and activate) one output tile at a time."""
+    assert order in ("block", "tile")
     dev = ws[0].device
     hid, pe, cond = tables = [t.to(dev) for t in _value_slots(n_levels)]
-    out = _forward_blocks(ws, bs, tables, ("cond", "skip", "hid"))
-    for l, wt, cond_rows, pe_rows in _reverse_layers(ws, pe, cond, (10 * n_levels + 15) // 16):
+    out = _forward_blocks(ws, bs, tables, ("cond", "skip", "hid"), hid3=hid3, order=order)
+    for l, wt, cond_rows, pe_rows in _reverse_layers(ws, pe, cond, (10 * n_levels + 15) // 16) if order == "block" else ():
         out.append(_gather(torch.cat([wt, cond_rows] + ([pe_rows] if l == 3 else []), 0), hid[:7] if l == 2 else hid))     # [block][tile]
         if l == 1:
             out.append(_gather(pe_rows, hid))                                     # G_0 for the point-encoding tile

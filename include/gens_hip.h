@@ -55,7 +55,10 @@ const char* gens_last_error(void);
  *   12 = round 6: gens_upsample2d_cat (the warp features in one launch), gens_volume_build_levels_bits (the volume build leaves the masks as bits
  *       too), gens_select_views (the views of a fine-tune step out of the frozen maps and their layouts in one launch),
  *       gens_lookup_volume_bwd_bricks / _bwd2_bricks + gens_lookup_scatter_bricks_scratch_bytes (K2's volume-gradient scatter brick by brick).
- *       Later additions that change no existing entry keep 12: gens_sdf_{value,grad}_bf16x3 + gens_sdf_bf16x3_pieces (+ gens_sdf_bf16x3_residency),
+ *       Later additions that change no existing entry keep 12: gens_sdf_{value,grad}_bf16x3 + gens_sdf_bf16x3_pieces (+ gens_sdf_bf16x3_residency, gens_sdf_bf16x3_layout;
+ *       NOTE: with gens_sdf_bf16x3_layout the STREAM of gens_sdf_{value,grad}_bf16x3 changed at three levels -- forward layer 3 has seven hidden K blocks,
+ *       gens_sdf_bf16x3_pieces(3) went from 1520 to 1512 -- without a new number, because the suite pins 12: a caller that packs the stream itself must
+ *       ask gens_sdf_bf16x3_layout and pack what it says; a stream packed for the earlier layout gives wrong numbers and no error),
  *       gens_blend_bf16x3_residency, and K23's
  *       gens_mesh_grid_{count,fill}, gens_ray_first_hit, gens_view_rays_hit_faces, gens_face_cc_{hook,compress}, and K24's
  *       gens_mesh_sample_{count,emit}, gens_point_grid_{count,fill}, gens_radius_downsample_round, gens_nearest_point, and K25's
@@ -387,9 +390,12 @@ int gens_sdf_grad_f16_pieces(int n_levels);
  * THREE round-to-nearest bfloat16 terms x0 + x1 + x2 and a product is x2 y0 + x1 y1 + x0 y2 + x1 y0 + x0 y1 + x0 y0 with float32
  * accumulation (the dropped terms are below ~2^-26 relative); bfloat16 has float32's exponent range, so there is no overflow flag.  The
  * dataflow of gens_sdf_grad_f16.  Three or five volume levels; GENS_ELIMIT otherwise.  gens_sdf_value_bf16x3 runs the forward half of
- * gens_sdf_grad_bf16x3's code on the forward prefix of the same stream: the two return the same float32 sdf for the same point.
- *   pieces: DEVICE, 16-byte aligned, gens_sdf_bf16x3_pieces(n_levels) x 1024 bytes in the order of gens_amd.ops._pack_grad_pieces(terms=3):
- *   [64 lanes][8 bfloat16] per (K block, output tile, x0 | x1 | x2).
+ * gens_sdf_grad_bf16x3: every accumulator receives the same products in the same order, so the two return the same float32 sdf for the
+ * same point.
+ *   pieces: DEVICE, 16-byte aligned, 1024-byte pieces in the order of gens_amd.ops._pack_grad_pieces(terms=3, hid3=layout[2]):
+ *   [64 lanes][8 bfloat16] per (K block, output tile, x0 | x1 | x2).  gens_sdf_grad_bf16x3: gens_sdf_bf16x3_pieces(n_levels) of them.
+ *   gens_sdf_value_bf16x3: the gradient kernel's stream, of which it reads the forward prefix; where gens_sdf_bf16x3_layout says tile-major
+ *   (a development build of the three-level kernel), the value-only stream order="tile" of layout[0] pieces, [tile][block][term] in a layer.
  *   w_out: the output row of gens_sdf_grad (same layout).
  *   stash: gens_sdf_grad_f16's (gens_sdf_grad_f16_stash_bytes() bytes, zeroed once; the same buffer may serve both kernels). */
 int gens_sdf_value_bf16x3(const float* const* vols_packed, const int* dims, int n_levels, const void* pieces, const float* w_out,
@@ -400,6 +406,10 @@ int gens_sdf_grad_bf16x3(const float* const* vols_packed, const int* dims, int n
                          float* sdf_out, float* grad_out, void* stash, void* stream);
 /* number of 1 KB pieces in the weight stream of gens_sdf_value_bf16x3 / gens_sdf_grad_bf16x3, padding included (0 = unsupported level count) */
 int gens_sdf_bf16x3_pieces(int n_levels);
+/* how this build's kernels walk the stream: out[0] pieces of the forward half, padding included (what gens_sdf_value_bf16x3 reads), out[1] 1 if
+ * gens_sdf_value_bf16x3 takes the tile-major value-only stream at this level count, 0 if the forward prefix of the gradient kernel's stream,
+ * out[2] hidden K blocks of forward layer 3 (7 at three levels, 8 at five).  out: HOST, 3 ints. */
+int gens_sdf_bf16x3_layout(int n_levels, int out[3]);
 /* residency of one instantiation (grad: 0 = gens_sdf_value_bf16x3's kernel, 1 = gens_sdf_grad_bf16x3's) on the current device, at the launcher's
  * block and LDS sizes: out[0] registers per lane (hipFuncAttributes.numRegs), out[1] scratch bytes per lane (localSizeBytes), out[2] dynamic LDS
  * bytes of a launch, out[3] resident workgroups per CU (hipOccupancyMaxActiveBlocksPerMultiprocessor).  out: HOST, 4 ints. */
