@@ -422,6 +422,79 @@ def mesh_report(vertices, triangles, device=None):
     return ops.mesh_topology(torch.from_numpy(v_np).to(dev), torch.from_numpy(t_np).to(dev)).report()
 
 
+def _mesh_arrays(who, vertices, triangles):
+    """Host arrays of a mesh with any indices -> (vertices (V, 3) float64, triangles (F, 3) int32, the input's integer type); ValueError for
+    arrays that are not (n, 3), indices that are not whole numbers or do not fit int32."""
+    v_np, t_np = np.asarray(as_numpy(vertices)), np.asarray(as_numpy(triangles))
+    if any(x.size and (x.ndim != 2 or x.shape[1] != 3) for x in (v_np, t_np)):
+        raise ValueError(f"{who}: vertices {v_np.shape}, triangles {t_np.shape}: expected (V, 3) and (F, 3)")
+    if t_np.size and not np.issubdtype(t_np.dtype, np.integer):
+        raise ValueError(f"{who}: triangles of {t_np.dtype}: whole numbers")
+    if t_np.size and (t_np.min() < -2 ** 31 or t_np.max() >= 2 ** 31):
+        raise ValueError(f"{who}: a triangle index does not fit int32")
+    kind = t_np.dtype if np.issubdtype(t_np.dtype, np.integer) else np.dtype(np.int32)
+    return np.ascontiguousarray(v_np, dtype=np.float64).reshape(-1, 3), np.ascontiguousarray(t_np.reshape(-1, 3), dtype=np.int32), kind
+
+
+def carry_repair_attributes(triangles, vertex_source, face_source, normals=None, colors=None, seen=None):
+    """The attributes of a repaired mesh (ops.repair_mesh's triangles', vertex_source, face_source as host arrays) from those of its input:
+    a kept vertex takes its source's row; a centroid, whose fill faces (b, a, centroid) name its loop once per vertex, takes the loop's
+    mean normal, renormalised (a zero row if the mean is zero), the mean colour rounded to the nearest whole number, and `seen` only if
+    the whole loop is seen -> {name: array} for the attributes given."""
+    kept = vertex_source >= 0
+    fill = triangles[face_source < 0]
+    fill = fill[~kept[fill[:, 2]]] if len(fill) else fill          # (a loop of three has no centroid: its face carries nothing)
+    count = np.zeros(len(vertex_source))
+    np.add.at(count, fill[:, 2], 1.0)
+    out = {}
+    for name, a in (("normals", normals), ("colors", colors), ("seen", seen)):
+        if a is None:
+            continue
+        a = np.asarray(a)
+        rows = np.zeros((len(vertex_source),) + a.shape[1:], dtype=a.dtype)
+        rows[kept] = a[vertex_source[kept]]
+        if len(fill):
+            total = np.zeros(rows.shape, dtype=np.float64)
+            np.add.at(total, fill[:, 2], a[vertex_source[fill[:, 1]]].astype(np.float64))
+            mean = total[~kept] / count[~kept].reshape((-1,) + (1,) * (a.ndim - 1))
+            if name == "normals":
+                length = np.sqrt((mean * mean).sum(axis=-1, keepdims=True))
+                mean = np.where(length > 0.0, mean / np.where(length > 0.0, length, 1.0), 0.0)
+            elif name == "colors":
+                mean = np.rint(mean) if np.issubdtype(a.dtype, np.integer) else mean
+            else:
+                mean = mean == 1.0                                 # every vertex of the loop is seen
+            rows[~kept] = mean.astype(a.dtype)
+        out[name] = rows
+    return out
+
+
+@torch.no_grad()
+def repair_mesh(vertices, triangles, normals=None, colors=None, seen=None, device=None, **kw):
+    """ops.repair_mesh (K38: duplicate and invalid faces dropped, pinches and non-manifold edges split, small components dropped,
+    components re-oriented, small holes closed) for host meshes, numpy in and out like the cleaners: vertices (V,3), triangles (F,3) (arrays
+    or tensors, any indices); kw: ops.repair_mesh's split, orient, min_component_faces, max_hole_edges, dedupe -> (vertices' (V',3) float64,
+    triangles' (F',3) of the input's integer type, attrs).  attrs["vertex_source"] (V',), attrs["face_source"] (F',) int32 (-1: a centroid
+    / a fill face), attrs["face_flipped"] (F',) bool, attrs["stats"]: ops.repair_mesh's counts; normals / colors / seen (V, ...), where given,
+    come back under those names carried through vertex_source (carry_repair_attributes: a centroid takes its loop's renormalised mean
+    normal, rounded mean colour and the AND of `seen`).  ValueError, before the device is looked at, for what ops.repair_request refuses, for
+    arrays that are not (n, 3), indices that are not whole numbers or do not fit int32, and for an attribute whose length is not V."""
+    from . import ops
+    who = "repair_mesh"
+    opt = ops.repair_request(who, **kw)
+    v_np, t_np, kind = _mesh_arrays(who, vertices, triangles)
+    given = {name: as_numpy(a) for name, a in (("normals", normals), ("colors", colors), ("seen", seen)) if a is not None}
+    for name, a in given.items():
+        if len(a) != len(v_np):
+            raise ValueError(f"{who}: {name} has {len(a)} rows for {len(v_np)} vertices")
+    dev = device_of(vertices, triangles, device=device)
+    out_v, out_t, vertex_source, face_source, flipped, stats = ops.repair_mesh(torch.from_numpy(v_np).to(dev), torch.from_numpy(t_np).to(dev), **opt)
+    out_t, vertex_source, face_source = out_t.cpu().numpy(), vertex_source.cpu().numpy(), face_source.cpu().numpy()
+    attrs = carry_repair_attributes(out_t, vertex_source, face_source, **given)
+    attrs.update(vertex_source=vertex_source, face_source=face_source, face_flipped=flipped.cpu().numpy(), stats=stats)
+    return out_v.cpu().numpy(), out_t.astype(kind), attrs
+
+
 def dilate_masks(masks, radius=11):
     """utils/clean_mesh.py:119-125: masks (nv,H,W[,3]) > 0.5, dilated by a disk of `radius` pixels (skimage.morphology.disk)."""
     from scipy import ndimage

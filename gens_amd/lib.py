@@ -258,6 +258,12 @@ SIGNATURES = {
     "gens_mesh_vertex_classify": [_p, _p, _p, _p, _p, _l, _l, _l, _p, _p, _p, _p],
     "gens_mesh_pseudonormals": [_p, _p, _l, _l, _l, _p, _p, _p, _p, _p, _p, _p, _p],
     "gens_mesh_distance_sign": [_p, _l, _p, _p, _p, _p, _p, _l, _l, _l, _p, _p, _p, _p, _p, _p, _p, _p],
+    "gens_mesh_face_keys": [_p, _l, _l, _p, _p, _p],
+    "gens_mesh_split_corners": [_p, _p, _p, _p, _l, _l, _l, _p, _p, _p],
+    "gens_mesh_orient_pairs": [_p, _p, _l, _l, _p, _p],
+    "gens_mesh_apply_flips": [_p, _p, _l, _p, _p],
+    "gens_mesh_loop_centroids": [_p, _l, _p, _p, _l, _l, _p, _l, _p, _p],
+    "gens_mesh_fill_emit": [_p, _l, _l, _p, _p, _l, _p, _p, _p, _p, _l, _l, _p, _p],
 }
 
 _lib = None

@@ -115,6 +115,9 @@ class GenS(nn.Module):
         topology = confs.get("mesh_topology", None)             # optional: ... and take the topology report of the returned mesh (ops.mesh_topology, K37); True
         if topology is not None:
             self.implicit_surface.mesh_topology = bool(topology)
+        repair = confs.get("mesh_repair", None)                 # optional: ... and repair the mesh on the device before that report, the attributes and the texture (ops.repair_mesh, K38); True or a dict of its keywords
+        if repair is not None:
+            self.implicit_surface.mesh_repair = repair if isinstance(repair, bool) else dict(repair)
         texture = confs.get("mesh_texture", None)               # optional: extract_geometry / validate also return a texture atlas of the mesh (texture_mesh, K34); the tile edge in texels or its keywords
         if texture is not None:
             self.implicit_surface.mesh_texture = dict(texture) if hasattr(texture, "keys") else texture

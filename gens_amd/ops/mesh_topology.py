@@ -170,6 +170,7 @@ def mesh_topology(vertices, triangles, normals=False):
     if nt and nv:
         corner_start[1:] = torch.cumsum(torch.bincount(corner_vertex.long(), minlength=nv + 1)[:nv], 0).to(_i32)
     del corner_vertex
+    topo.corner_order, topo.corner_start = corner_order, corner_start          # (the vertices' corner segments: K38's split walks them again)
     _topology_section("vertex_classify")
     topo.valence, topo.fans = torch.empty(nv, device=dev, dtype=_i32), torch.empty(nv, device=dev, dtype=_i32)
     topo.vertex_flags = torch.empty(nv, device=dev, dtype=_u8)

@@ -70,7 +70,9 @@ const char* gens_last_error(void);
  *       gens_surface_pack, and K32's gens_fuse_depth_maps, gens_fused_points, and K33's gens_cluster_keys, gens_cluster_triangles,
  *       gens_cluster_solve, and K34's gens_texture_points, gens_texture_snap, gens_texture_keep_better,
  *       gens_texture_pack, gens_texture_uv, and K35's gens_mesh_shade, and K36's gens_mesh_closest_point, and K37's gens_mesh_edge_keys,
- *       gens_mesh_edge_classify, gens_mesh_fan_pairs, gens_mesh_vertex_classify, gens_mesh_pseudonormals, gens_mesh_distance_sign. */
+ *       gens_mesh_edge_classify, gens_mesh_fan_pairs, gens_mesh_vertex_classify, gens_mesh_pseudonormals, gens_mesh_distance_sign, and K38's
+ *       gens_mesh_face_keys, gens_mesh_split_corners, gens_mesh_orient_pairs, gens_mesh_apply_flips, gens_mesh_loop_centroids,
+ *       gens_mesh_fill_emit. */
 int gens_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -1407,6 +1409,82 @@ int gens_mesh_distance_sign(const double* queries, int64_t n_queries, const doub
                             const double* face_normal, const double* edge_normal, const double* vertex_normal,
                             const int32_t* edge_of_halfedge, const uint8_t* edge_class, const uint8_t* vertex_flags, double* signed_out,
                             void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * K38  Mesh repair: drop invalid and duplicate faces, split pinches and non-manifold edges, drop small components, re-orient, close small
+ *      holes (ops.repair_mesh, io.repair_mesh, python -m gens_amd.repair_mesh, ImplicitSurface.extract_geometry(repair=)),
+ *      csrc/k38_mesh_repair.hip.  tests/mesh_repair_reference.py restates all of it in numpy with dicts and loops.  vertices (V, 3) float64,
+ *      triangles (T, 3) int32; V < 2^31 and 3 T < 2^31.  VALID, half-edge, corner, edge class, fan, face component: K37's definitions.
+ *
+ *   The stages, in this order.  Each is an option; every one is deterministic (no float atomics, nothing depends on launch order).
+ *     a. DEDUPE.  Faces that are not VALID are dropped (always: a face with an index outside the vertices has no place in the result).  With
+ *        the option on, among valid faces with the same vertex SET, in any winding, the one with the smallest face id survives.  The
+ *        survivors keep their order.
+ *     b. SPLIT.  Take K37's topology of the surviving faces.  Every referenced vertex v with fans[v] = k becomes k vertices at v's position,
+ *        one per fan; a corner takes the copy of its fan.  New ids: the original vertices in ascending id, within a vertex its fans in
+ *        ascending label (the smallest corner id).  Unreferenced vertices are dropped.  Off: vertices and indices stay as they are.
+ *        ONE ROUND SUFFICES (the bound on rounds is 1).  Proof.  Fans join only across edges of class 2 and 3, which have exactly two uses,
+ *        so around a vertex a every face of a fan is joined to at most one other face across each of its two edges at a: a fan is a path or
+ *        a cycle of faces.  (i) An edge (a, b) of class 2 or 3 joins its two faces' corners at a and at b, so both uses name the same pair of
+ *        copies: the edge survives with its two uses and its class.  (ii) A use of an edge (a, b) of class 1 or 4 is an edge across which
+ *        nothing is joined, so within its fan at a its face is an END of a path; a path has two ends, so at most two uses of (a, b) name the
+ *        copy a' of that fan, and no edge at a' has more than two uses: no class-4 edge is left.  (iii) The corners at a copy a' are those
+ *        of one old fan, and the class-2 and class-3 edges that joined them survive by (i), so a' has one fan: no pinch is left.  Two uses
+ *        that pair up on a new edge by (ii) lie in one fan, hence were already in one face component: the components do not change.
+ *     c. SMALL COMPONENTS (min_component_faces = m, 0 = off).  In K37's topology of the split mesh, faces whose face_component has fewer
+ *        than m faces are dropped, and with them the vertices no face refers to any more; both keep their order.
+ *     d. ORIENT.  A union-find on 2 T' nodes, node 2 f + s.  An edge of class 2 with the faces fa, fb of its two half-edges joins (fa, 0) -
+ *        (fb, 0) and (fa, 1) - (fb, 1); an edge of class 3 joins (fa, 0) - (fb, 1) and (fa, 1) - (fb, 0).  Labels are smallest members.  A
+ *        component is NON-ORIENTABLE where label(f, 0) == label(f, 1): its faces are left alone and it is counted.  Otherwise the faces
+ *        with label(f, 0) < label(f, 1) are the side of the component's smallest face, min(label(f, 0), label(f, 1)) / 2.  The side with more
+ *        faces keeps its winding; on a tie the smallest face's side does.  Every face of the other side becomes (a, c, b).  The sides are
+ *        counted by sort and search.
+ *     e. FILL (max_hole_edges = n, 0 = off; needs b and d).  In K37's topology of the oriented mesh every boundary vertex has exactly two
+ *        class-1 edges, so the union of the class-1 edges over the vertices gives the loops, named by their smallest vertex.  A loop of
+ *        3 <= length <= n edges is closed, unless one of its edges belongs to a face of a non-orientable component or all of them belong to
+ *        one face (a lone triangle: its closing face would have that face's vertex set, which (a) drops from a second pass).  The boundary half-edge
+ *        a -> b of a closed loop gets the face (b, a, c): c is a new vertex at the loop's centroid -- the float64 sum of the loop's vertices
+ *        in ascending vertex id, starting from 0, per component, then divided by their number -- or, for a loop of 3, the loop's third
+ *        vertex, and then only the loop's smallest boundary half-edge gets a face.  New faces follow the kept faces in ascending boundary
+ *        half-edge id, new vertices follow the kept vertices in ascending loop name.  Longer loops stay open.  A centroid fan over a
+ *        strongly non-planar loop can intersect itself or the mesh; that is not detected.
+ *     Results: vertices' (V', 3) float64, kept ones bit-identical to their sources; triangles' (T', 3) int32; vertex_source (V') int32, the
+ *       original vertex or -1 for a centroid; face_source (T') int32, the original face or -1 for a fill face; face_flipped (T') bool.
+ *
+ *   gens_mesh_face_keys: per face, key_major (T) int64 = the smallest index and key_minor (T) int64 = (middle << 32) | largest; both
+ *     INT64_MAX for a face that is not valid.  Two stable sorts (minor, then major) leave equal triples adjacent in ascending face id.
+ *   gens_mesh_split_corners: per vertex, one thread walks the vertex's corners (corner_order, corner_start, corner_label as in
+ *     gens_mesh_vertex_classify) in ascending corner id.  vertex_base (V) int32: the exclusive prefix sum of K37's fans.  A corner that is
+ *     its own label is the r-th root of the walk: new_corner[c] = vertex_base[v] + r and vertex_source[that] = v; another corner takes
+ *     new_corner[label], which the same thread wrote before.  new_corner (3 T) int32 is first filled with -1, what corners of faces that
+ *     are not valid keep; vertex_source (n_new) int32.  A root whose id would reach n_new is skipped.
+ *   gens_mesh_orient_pairs: per edge, pairs (2 E, 2) int32: the two joins of (d) for an edge of class 2 or 3, with fa, fb the faces of
+ *     edge_halfedges' two entries; (-1, -1) for other edges.  The rows go through gens_face_cc_hook / gens_face_cc_compress with 2 T nodes.
+ *   gens_mesh_apply_flips: per face, out = (a, c, b) where flip (T) uint8 is not zero, else (a, b, c).
+ *   gens_mesh_loop_centroids: per loop, one thread walks loop_vertices [loop_start[l], loop_start[l + 1]) -- the n_rim boundary vertices
+ *     sorted by loop name, then id -- and writes the centroid to row loop_slot[l] of centroids (n_centroids, 3) float64; a slot outside
+ *     [0, n_centroids) writes nothing.
+ *   gens_mesh_fill_emit: per boundary half-edge.  rim_halfedges (n_rim) int32 in ascending order; rim_slot (n_rim) int32: the row of faces
+ *     (n_fill, 3) int32 to write, outside [0, n_fill) for none; loop_of_vertex (V) int32: the loop's rank, -1 off the boundary; loop_apex
+ *     (n_loops) int32: the id of the loop's centroid vertex, below zero for a loop of three, whose third vertex is found by a walk of the
+ *     loop's segment.  A row that cannot be formed (an id outside its range) is written as (-1, -1, -1).
+ *   Arguments are checked before any launch.  GENS_EINVAL: a negative count; more edges than half-edges, more new vertices than
+ *     half-edges, more loops than rim vertices, more centroids than loops, more rim half-edges than vertices or than half-edges, more fill
+ *     faces than rim half-edges; a half-edge count that is no multiple of 3; a null pointer that the given counts would have the launch
+ *     read or write.  GENS_ELIMIT: V or 3 T >= 2^31.  Counts of zero succeed without the launch they would size.  Ids outside their
+ *     ranges are skipped, never read through.  The ABI version stays 12: no existing entry changes.
+ * ---------------------------------------------------------------------------------------------------------- */
+int gens_mesh_face_keys(const int32_t* triangles, int64_t n_faces, int64_t n_vertices, int64_t* key_major, int64_t* key_minor, void* stream);
+int gens_mesh_split_corners(const int32_t* corner_order, const int32_t* corner_start, const int32_t* corner_label, const int32_t* vertex_base,
+                            int64_t n_vertices, int64_t n_halfedges, int64_t n_new, int32_t* new_corner, int32_t* vertex_source, void* stream);
+int gens_mesh_orient_pairs(const int32_t* edge_halfedges, const uint8_t* edge_class, int64_t n_edges, int64_t n_faces, int32_t* pairs,
+                           void* stream);
+int gens_mesh_apply_flips(const int32_t* triangles, const uint8_t* flip, int64_t n_faces, int32_t* out, void* stream);
+int gens_mesh_loop_centroids(const double* vertices, int64_t n_vertices, const int32_t* loop_start, const int32_t* loop_vertices,
+                             int64_t n_loops, int64_t n_rim, const int32_t* loop_slot, int64_t n_centroids, double* centroids, void* stream);
+int gens_mesh_fill_emit(const int32_t* triangles, int64_t n_faces, int64_t n_vertices, const int32_t* rim_halfedges, const int32_t* rim_slot,
+                        int64_t n_rim, const int32_t* loop_of_vertex, const int32_t* loop_start, const int32_t* loop_vertices,
+                        const int32_t* loop_apex, int64_t n_loops, int64_t n_fill, int32_t* faces, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K14  C (m x n) = A^T B for tall row-major operands A (k x m), B (k x n), k >> m, n: the weight-gradient product of the training
