@@ -401,14 +401,17 @@ def compare_meshes(va, ta, vb, tb, device=None, **kw):
 
 
 @torch.no_grad()
-def mesh_report(vertices, triangles, device=None):
+def mesh_report(vertices, triangles, device=None, roughness=False):
     """ops.mesh_topology(...).report() (K37) for a host mesh, numpy in like the cleaners: vertices (V,3), triangles (F,3) (arrays or tensors)
     -> the dict of Python numbers: vertices, vertices_referenced, faces, faces_invalid, edges and their counts by class (boundary, manifold,
     flipped, non-manifold), vertices_pinched, vertices_nonmanifold, components, largest_component_faces, boundary_components, euler, closed,
     oriented, manifold, watertight, genus (None unless watertight), area, volume.  Any indices are accepted: a face with an index outside
-    the vertices or a repeated one is counted as invalid and takes part in nothing else.  ValueError, before the device is looked at, for
-    arrays that are not (n, 3), indices that are not whole numbers or do not fit int32."""
+    the vertices or a repeated one is counted as invalid and takes part in nothing else.  roughness=True: a further key "roughness", ops.
+    mesh_roughness's report {edges, mean, rms, max} of the dihedral angles (K39).  ValueError, before the device is looked at, for arrays
+    that are not (n, 3), indices that are not whole numbers or do not fit int32, a `roughness` that is no bool."""
     from . import ops
+    if not isinstance(roughness, bool):
+        raise ValueError(f"mesh_report: roughness = {roughness!r}: True or False")
     v_np, t_np = np.asarray(as_numpy(vertices)), np.asarray(as_numpy(triangles))
     if any(x.size and (x.ndim != 2 or x.shape[1] != 3) for x in (v_np, t_np)):
         raise ValueError(f"mesh_report: vertices {v_np.shape}, triangles {t_np.shape}: expected (V, 3) and (F, 3)")
@@ -419,7 +422,11 @@ def mesh_report(vertices, triangles, device=None):
     v_np = np.ascontiguousarray(v_np, dtype=np.float64).reshape(-1, 3)
     t_np = np.ascontiguousarray(t_np.reshape(-1, 3), dtype=np.int32)
     dev = device_of(vertices, triangles, device=device)
-    return ops.mesh_topology(torch.from_numpy(v_np).to(dev), torch.from_numpy(t_np).to(dev)).report()
+    if not roughness:
+        return ops.mesh_topology(torch.from_numpy(v_np).to(dev), torch.from_numpy(t_np).to(dev)).report()
+    dv, dt = torch.from_numpy(v_np).to(dev), torch.from_numpy(t_np).to(dev)
+    topo = ops.mesh_topology(dv, dt, normals=True)
+    return {**topo.report(), "roughness": ops.mesh_roughness(dv, dt, topology=topo)[1]}
 
 
 def _mesh_arrays(who, vertices, triangles):
@@ -493,6 +500,36 @@ def repair_mesh(vertices, triangles, normals=None, colors=None, seen=None, devic
     attrs = carry_repair_attributes(out_t, vertex_source, face_source, **given)
     attrs.update(vertex_source=vertex_source, face_source=face_source, face_flipped=flipped.cpu().numpy(), stats=stats)
     return out_v.cpu().numpy(), out_t.astype(kind), attrs
+
+
+@torch.no_grad()
+def smooth_mesh(vertices, triangles, colors=None, seen=None, device=None, **kw):
+    """ops.smooth_mesh (K39: Laplacian / Taubin smoothing with uniform or cotangent weights) for host meshes, numpy in and out like the
+    cleaners: vertices (V,3), triangles (F,3) (arrays or tensors, any indices); kw: ops.smooth_mesh's iterations, lam, mu, weights,
+    fix_boundary, measure and pinned ((V,) bool) -> (vertices' (V,3) float64, triangles (F,3) as they came, attrs).  attrs["stats"]:
+    ops.smooth_mesh's stats; colors / seen (V, ...), where given, come back under those names unchanged (the vertex count does not change).
+    Normals are not accepted: they no longer describe the surface (recompute them: vertex_attributes, or ops.mesh_topology(normals=True)).
+    ValueError, before the device is looked at, for what ops.smooth_request refuses, a `normals` keyword, arrays that are not (n, 3),
+    indices that are not whole numbers or do not fit int32, and for an attribute or a `pinned` whose length is not V."""
+    from . import ops
+    who = "smooth_mesh"
+    if "normals" in kw:
+        raise ValueError(f"{who}: normals are not carried: after smoothing they no longer describe the surface (recompute them)")
+    pinned = kw.pop("pinned", None)
+    opt = ops.smooth_request(kw, who)
+    v_np, t_np, _ = _mesh_arrays(who, vertices, triangles)
+    given = {name: as_numpy(a) for name, a in (("colors", colors), ("seen", seen)) if a is not None}
+    if pinned is not None:
+        pinned = np.asarray(as_numpy(pinned))
+        if pinned.dtype != np.bool_ or pinned.ndim != 1:
+            raise ValueError(f"{who}: pinned is {pinned.shape} {pinned.dtype}, expected (V,) bool")
+    for name, a in {**given, **({} if pinned is None else {"pinned": pinned})}.items():
+        if len(a) != len(v_np):
+            raise ValueError(f"{who}: {name} has {len(a)} rows for {len(v_np)} vertices")
+    dev = device_of(vertices, triangles, device=device)
+    out_v, _, stats = ops.smooth_mesh(torch.from_numpy(v_np).to(dev), torch.from_numpy(t_np).to(dev),
+                                      pinned=None if pinned is None else torch.from_numpy(np.ascontiguousarray(pinned)).to(dev), **opt)
+    return out_v.cpu().numpy(), as_numpy(triangles), {**given, "stats": stats}
 
 
 def dilate_masks(masks, radius=11):

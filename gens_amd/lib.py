@@ -264,6 +264,10 @@ SIGNATURES = {
     "gens_mesh_apply_flips": [_p, _p, _l, _p, _p],
     "gens_mesh_loop_centroids": [_p, _l, _p, _p, _l, _l, _p, _l, _p, _p],
     "gens_mesh_fill_emit": [_p, _l, _l, _p, _p, _l, _p, _p, _p, _p, _l, _l, _p, _p],
+    "gens_mesh_corner_cot": [_p, _p, _l, _l, _p, _p],
+    "gens_mesh_edge_weights": [_p, _p, _p, _l, _l, _p, _p],
+    "gens_mesh_laplacian_step": [_p, _l, _p, _p, _p, _l, _p, _l, _p, _d, _p, _p, _p, _p],
+    "gens_mesh_dihedral": [_p, _l, _p, _p, _l, _p, _p],
 }
 
 _lib = None

@@ -1,8 +1,11 @@
-"""python -m gens_amd.mesh_report MESH.{ply,obj} [--device D]
+"""python -m gens_amd.mesh_report MESH.{ply,obj} [--roughness] [--device D]
 
 The topology report of a triangle mesh on the device (K37; io.mesh_report, ops.mesh_topology), printed as one JSON line: vertices, faces and
 edges by class (boundary, manifold, flipped, non-manifold), pinched vertices, components, boundary loops, the Euler characteristic, whether
-the mesh is closed, oriented, manifold and watertight, its genus if it is, its area and its signed volume."""
+the mesh is closed, oriented, manifold and watertight, its genus if it is, its area and its signed volume.
+
+--roughness adds the key "roughness": the number, mean, RMS and maximum of the dihedral angles between the normals of the faces either
+side of every manifold edge (K39; ops.mesh_roughness)."""
 import argparse
 import json
 import sys
@@ -14,11 +17,12 @@ from .compare_meshes import read_mesh
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m gens_amd.mesh_report", description=__doc__.split("\n\n")[1])
     ap.add_argument("mesh", metavar="MESH.{ply,obj}")
+    ap.add_argument("--roughness", action="store_true", help="add the dihedral roughness report (K39)")
     ap.add_argument("--device", default=None)
     args = ap.parse_args(argv)
     try:
         vertices, triangles = read_mesh(args.mesh)
-        out = gio.mesh_report(vertices, triangles, device=args.device)
+        out = gio.mesh_report(vertices, triangles, device=args.device, **({"roughness": True} if args.roughness else {}))
     except (ValueError, OSError, RuntimeError) as e:     # a file that cannot be read; a mesh that is no (n, 3) arrays
         print(f"gens_amd.mesh_report: {e}", file=sys.stderr)
         return 2

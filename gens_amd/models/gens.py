@@ -118,6 +118,9 @@ class GenS(nn.Module):
         repair = confs.get("mesh_repair", None)                 # optional: ... and repair the mesh on the device before that report, the attributes and the texture (ops.repair_mesh, K38); True or a dict of its keywords
         if repair is not None:
             self.implicit_surface.mesh_repair = repair if isinstance(repair, bool) else dict(repair)
+        smooth = confs.get("mesh_smooth", None)                 # optional: ... and smooth the mesh on the device after the repair (ops.smooth_mesh, K39); True or a dict of its keywords
+        if smooth is not None:
+            self.implicit_surface.mesh_smooth = smooth if isinstance(smooth, bool) else dict(smooth)
         texture = confs.get("mesh_texture", None)               # optional: extract_geometry / validate also return a texture atlas of the mesh (texture_mesh, K34); the tile edge in texels or its keywords
         if texture is not None:
             self.implicit_surface.mesh_texture = dict(texture) if hasattr(texture, "keys") else texture

@@ -645,6 +645,18 @@ class ImplicitSurface(nn.Module):
             raise ValueError(f"repair = {repair!r}: True, or a dict of ops.repair_mesh's keywords (None or False: off)")
         return ops.repair_request("repair", **repair)
 
+    mesh_smooth = None             # True or a dict of ops.smooth_mesh's keywords (iterations, lam, mu, weights, fix_boundary, measure): extract_geometry /
+                                   # validate smooth the mesh on the device (K39) after the repair -> last_smooth_stats.  None / False: off
+    last_smooth_stats = None       # ops.smooth_mesh's stats of the last extract_geometry call, displacements in lattice spacings (None: that call did not smooth)
+
+    def _smooth_request(self, smooth):
+        """The smoothing a mesh call asks for (None: the attribute `mesh_smooth`) -> a dict of ops.smooth_mesh's checked keywords, or None
+        for off (None, False).  ValueError for anything but None, a bool or a dict that ops.smooth_request accepts."""
+        smooth = self.mesh_smooth if smooth is None else smooth
+        if smooth is None or smooth is False:
+            return None
+        return ops.smooth_request(smooth, "smooth")
+
     mesh_texture = None            # the tile edge in texels (3 to 64), or a dict of texture_mesh's keywords (texels, snap, max_move, chunk):
                                    # extract_geometry / validate also return a texture atlas of the mesh (texture_mesh, K34).  None / False / 0:
                                    # off (DESIGN.md, section 5k)
@@ -1257,7 +1269,7 @@ class ImplicitSurface(nn.Module):
         return out
 
     def extract_geometry(self, volumes, bound_min, bound_max, resolution, threshold, shard=None, sparse=None, sparse_mesh=None, attributes=None,
-                         views=None, simplify=None, texture=None, simplify_error=None, topology=None, repair=None):
+                         views=None, simplify=None, texture=None, simplify_error=None, topology=None, repair=None, smooth=None):
         """-> vertices (V,3) float64, triangles (T,3) int32 as numpy arrays (implicit_surface.py:407-427).  The SDF lattice and
         the marching cubes both run on the device (the reference: 512 D2H copies + PyMCubes on the host); only the mesh is copied.
         sparse: sdf_grid's option of that name, with this call's threshold.  sparse_mesh (default: the attribute of that name, None = off):
@@ -1295,6 +1307,13 @@ class ImplicitSurface(nn.Module):
         last_mesh_topology, the attributes and the atlas are those of the mesh this call returns.  self.last_repair_stats: its counts and,
         with topology on, "topology_before", the report of the mesh before the repair.  Off: nothing is launched, last_repair_stats is None
         and the mesh is what it was.  ValueError before any launch for another value or what ops.repair_request refuses.
+        smooth (default: the attribute `mesh_smooth`; None or False = off): True, or a dict of ops.smooth_mesh's keywords (iterations, lam,
+        mu, weights, fix_boundary, measure).  The device-resident mesh is smoothed in index coordinates (K39: Taubin's lambda | mu steps,
+        or plain Laplacian ones with mu = 0; the triangles are untouched) after the simplification, its simplify_error comparison and the
+        repair, and before the topology report, the attribute pass, the texture pass and the read-back, so that normals, colours, atlas and
+        report are those of the mesh this call returns.  self.last_smooth_stats: ops.smooth_mesh's stats, displacements in lattice
+        spacings.  Off: nothing is launched, last_smooth_stats is None and the mesh is what it was.  ValueError before any launch for
+        what ops.smooth_request refuses.
         texture (default: the attribute `mesh_texture`; None, False or 0 = off): the tile edge in texels (3 to 64) or a dict of texture_mesh's
         keywords (texels, snap, max_move, chunk) -> a further result after the attribute dict (whose place holds None when only the
         texture is asked for): texture_mesh's dict for the returned mesh (K34), computed after marching cubes and
@@ -1306,6 +1325,7 @@ class ImplicitSurface(nn.Module):
         simplify_error = self._simplify_error_request(simplify_error, simplify)
         topology = self._topology_request(topology)
         repair = self._repair_request(repair)
+        smooth = self._smooth_request(smooth)
         texture = self._texture_option(texture)
         if texture is not None:
             texture = {"threshold": threshold, **texture}
@@ -1313,6 +1333,7 @@ class ImplicitSurface(nn.Module):
         self.last_simplify_stats = None
         self.last_mesh_topology = None
         self.last_repair_stats = None
+        self.last_smooth_stats = None
         route, brick = self._lattice_route(sparse, sparse_mesh, shard)
         mesh = None
         if route == "mesh":
@@ -1342,6 +1363,8 @@ class ImplicitSurface(nn.Module):
             vertices, triangles, _, _, _, self.last_repair_stats = ops.repair_mesh(vertices, triangles, **repair)
             if before is not None:
                 self.last_repair_stats["topology_before"] = before
+        if smooth is not None:
+            vertices, triangles, self.last_smooth_stats = ops.smooth_mesh(vertices, triangles, **smooth)
         if topology:
             self.last_mesh_topology = ops.mesh_topology(vertices, triangles).report()
         b_max, b_min = bound_max.detach().cpu().numpy(), bound_min.detach().cpu().numpy()
@@ -1362,7 +1385,7 @@ class ImplicitSurface(nn.Module):
     def validate(self, rays_o, rays_d, near, far, volumes, mask_volumes, imgs, features, match_features, intrs, c2ws, bound_min, bound_max,
                  hw, cos_anneal_ratio=1.0, step=None, extract_geometry=True, mesh_resolution=512, threshold=0.0, scene=None, shard=None, sparse=None,
                  sparse_mesh=None, mesh_attributes=None, surface_render=None, surface_fusion=None, mesh_simplify=None, mesh_texture=None,
-                 mesh_render=None, mesh_simplify_error=None, mesh_topology=None, mesh_repair=None):
+                 mesh_render=None, mesh_simplify_error=None, mesh_topology=None, mesh_repair=None, mesh_smooth=None):
         """shard (gens_amd.distributed.Shard, optional): render only this rank's contiguous ray range and evaluate only its lattice
         chunks; the (P, 8) image buffer / the lattice slabs are gathered over RCCL, so every rank returns the whole image.  The jitter
         of EVERY ray is drawn on every rank from the identically seeded CPU generator (the reference's draw order) and sliced with
@@ -1381,7 +1404,9 @@ class ImplicitSurface(nn.Module):
         when the simplification is off.  mesh_topology: extract_geometry's `topology` (True; default: the attribute of that name, None /
         False = off): self.last_mesh_topology holds the topology report of the returned mesh (K37).  mesh_repair: extract_geometry's `repair`
         (True or a dict of ops.repair_mesh's keywords; default: the attribute of that name, None / False = off): the mesh is repaired on the
-        device (K38) before the report, the attributes and the texture; self.last_repair_stats holds its counts.  mesh_texture: extract_geometry's
+        device (K38) before the report, the attributes and the texture; self.last_repair_stats holds its counts.  mesh_smooth: extract_geometry's
+        `smooth` (True or a dict of ops.smooth_mesh's keywords; default: the attribute of that name, None / False = off): the mesh is smoothed
+        on the device (K39) after the repair; self.last_smooth_stats holds its stats.  mesh_texture: extract_geometry's
         `texture` with this scene's views (the tile edge in texels or a dict of texture_mesh's keywords; default: the attribute of that name,
         None / False / 0 = off) -> outputs["texture"], ["texture_seen"], ["texture_uv"] (K34), which save_validation_outputs writes as an
         OBJ beside the PLY.  mesh_render (default: the attribute of that name, None / False = off; True, or a dict of render_mesh's keywords
@@ -1403,6 +1428,7 @@ class ImplicitSurface(nn.Module):
         mesh_simplify_error = self._simplify_error_request(mesh_simplify_error, mesh_simplify) if extract_geometry else None
         mesh_topology = self._topology_request(mesh_topology) if extract_geometry else False
         mesh_repair = self._repair_request(mesh_repair) if extract_geometry else None
+        mesh_smooth = self._smooth_request(mesh_smooth) if extract_geometry else None
         mesh_texture = self._texture_option(mesh_texture) if extract_geometry else None
         surface_fusion = self.surface_fusion if surface_fusion is None else surface_fusion
         if surface_fusion:
@@ -1437,7 +1463,7 @@ class ImplicitSurface(nn.Module):
                                          sparse_mesh=sparse_mesh, attributes=mesh_attributes, views=scene.views,
                                          simplify=0 if mesh_simplify is None else mesh_simplify, texture=0 if mesh_texture is None else mesh_texture,
                                          simplify_error=False if mesh_simplify_error is None else mesh_simplify_error, topology=mesh_topology,
-                                         repair=False if mesh_repair is None else mesh_repair)
+                                         repair=False if mesh_repair is None else mesh_repair, smooth=False if mesh_smooth is None else mesh_smooth)
             outputs["vertices"], outputs["triangles"] = mesh[0], mesh[1]
             for name, values in ((mesh[2] or {}) if len(mesh) >= 3 else {}).items():
                 outputs["vertex_" + name] = values

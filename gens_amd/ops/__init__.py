@@ -33,6 +33,7 @@ is what it was when ops was one module:
     ops.mesh_distance  K36: exact point-to-mesh distance over K23's grid (closest_point_on_mesh) and the two-sided comparison of two meshes (mesh_distance).
     ops.mesh_topology  K37: the edge table of a mesh, its topology report, pseudonormals (mesh_topology) and the signed distance (signed_distance_to_mesh).
     ops.mesh_repair  K38: mesh repair: duplicate faces, pinches and non-manifold edges split, small components, orientation, small holes (repair_mesh).
+    ops.mesh_fairing  K39: mesh fairing: Laplacian / Taubin smoothing with uniform or cotangent weights (smooth_mesh), mesh_laplacian, mesh_roughness.
 """
 from .base import *  # noqa: F401,F403
 from .volume import *  # noqa: F401,F403
@@ -58,3 +59,4 @@ from .mesh_render import *  # noqa: F401,F403
 from .mesh_distance import *  # noqa: F401,F403
 from .mesh_topology import *  # noqa: F401,F403
 from .mesh_repair import *  # noqa: F401,F403
+from .mesh_fairing import *  # noqa: F401,F403

@@ -33,6 +33,16 @@ def _union_labels(pairs, n):
     return label
 
 
+def area_volume(vertices, triangles, valid):
+    """The area and the signed volume of report(), as 0-d device tensors: vertices (V, 3) float64, triangles (T, 3) int32 with T > 0, valid (T)
+    bool (K37's face_valid; other faces add nothing).  volume = sum of a . (b x c) / 6.  No read-back."""
+    a, b, c = (vertices[torch.where(valid, triangles[:, k], torch.zeros_like(triangles[:, k])).long()] for k in range(3))
+    keep = valid.to(_f64)
+    area = (0.5 * torch.linalg.cross(b - a, c - a).square().sum(dim=1).sqrt() * keep).sum()
+    volume = ((a * torch.linalg.cross(b, c)).sum(dim=1) * keep).sum() / 6.0
+    return area, volume
+
+
 class MeshTopology:
     """What ops.mesh_topology found, as device tensors (E edges, T faces, V vertices; the definitions: include/gens_hip.h, K37):
         edges (E, 2) int32 (lo, hi) in ascending order; edge_count (E) int32; edge_forward (E) int32: uses that run lo -> hi;
@@ -41,7 +51,9 @@ class MeshTopology:
         valence (V) int32; fans (V) int32; vertex_flags (V) uint8: bit 0 referenced, 1 on a boundary edge, 2 on a non-manifold edge, 3 on a
         flipped edge, 4 pinched; corner_label (3 T) int32; face_component (T) int32: ops.face_components over the pairs of the class-2 and
         class-3 edges; with normals=True: face_normal (T, 3), edge_normal (E, 3), vertex_normal (V, 3) float64 (the sums, not normalised),
-        else None.  report(): the figures as Python numbers, in one read-back."""
+        else None; edge_start (E + 1) int32 and halfedge_order (3 T) int32: the edges' runs in the half-edges stably sorted by edge key, and
+        corner_start (V + 1), corner_order (3 T): the vertices' corner segments (K38 and K39 walk them again).  report(): the figures as Python
+        numbers, in one read-back."""
 
     def __init__(self, vertices, triangles):
         self.vertices, self.triangles = vertices, triangles
@@ -76,10 +88,7 @@ class MeshTopology:
             label = torch.sort(torch.where(valid, self.face_component, torch.full_like(self.face_component, nt)))[0]     # (not valid: last, under T)
             size = torch.searchsorted(label, label, right=True) - torch.searchsorted(label, label)                      # each face's component's size
             largest = torch.where(label < nt, size, torch.zeros_like(size)).max().to(_f64)
-            a, b, c = (self.vertices[torch.where(valid, self.triangles[:, k], torch.zeros_like(self.triangles[:, k])).long()] for k in range(3))
-            keep = valid.to(_f64)
-            area = (0.5 * torch.linalg.cross(b - a, c - a).square().sum(dim=1).sqrt() * keep).sum()
-            volume = ((a * torch.linalg.cross(b, c)).sum(dim=1) * keep).sum() / 6.0
+            area, volume = area_volume(self.vertices, self.triangles, valid)
         else:
             components = largest = area = volume = zero
         if nv:
@@ -144,6 +153,7 @@ def mesh_topology(vertices, triangles, normals=False):
     seg_start = torch.zeros(ne + 1, device=dev, dtype=_i32)
     seg_start[1:] = torch.cumsum(counts[:ne], 0).to(_i32)
     del key, counts
+    topo.edge_start, topo.halfedge_order = seg_start, order                    # (the edges' half-edge runs: K39's cotangent weights walk them again)
     _topology_section("edge_classify")
     topo.n_edges = ne
     topo.edges = torch.empty(ne, 2, device=dev, dtype=_i32)

@@ -72,7 +72,7 @@ const char* gens_last_error(void);
  *       gens_texture_pack, gens_texture_uv, and K35's gens_mesh_shade, and K36's gens_mesh_closest_point, and K37's gens_mesh_edge_keys,
  *       gens_mesh_edge_classify, gens_mesh_fan_pairs, gens_mesh_vertex_classify, gens_mesh_pseudonormals, gens_mesh_distance_sign, and K38's
  *       gens_mesh_face_keys, gens_mesh_split_corners, gens_mesh_orient_pairs, gens_mesh_apply_flips, gens_mesh_loop_centroids,
- *       gens_mesh_fill_emit. */
+ *       gens_mesh_fill_emit, and K39's gens_mesh_corner_cot, gens_mesh_edge_weights, gens_mesh_laplacian_step, gens_mesh_dihedral. */
 int gens_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -1485,6 +1485,62 @@ int gens_mesh_loop_centroids(const double* vertices, int64_t n_vertices, const i
 int gens_mesh_fill_emit(const int32_t* triangles, int64_t n_faces, int64_t n_vertices, const int32_t* rim_halfedges, const int32_t* rim_slot,
                         int64_t n_rim, const int32_t* loop_of_vertex, const int32_t* loop_start, const int32_t* loop_vertices,
                         const int32_t* loop_apex, int64_t n_loops, int64_t n_fill, int32_t* faces, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * K39  Mesh fairing: Laplacian and Taubin smoothing with uniform or cotangent weights, the vertex Laplacian and the dihedral roughness of
+ *      the edges (ops.smooth_mesh, ops.mesh_laplacian, ops.mesh_roughness, ops.smoothing_weights, io.smooth_mesh,
+ *      python -m gens_amd.smooth_mesh, python -m gens_amd.mesh_report --roughness, ImplicitSurface.extract_geometry(smooth=)),
+ *      csrc/k39_mesh_fairing.hip.  tests/mesh_smooth_reference.py restates all of it in numpy with dicts and loops.  vertices (V, 3)
+ *      float64, triangles (T, 3) int32 and K37's table of that mesh (E edges); V < 2^31 and 3 T < 2^31.  VALID, half-edge, edge, edge
+ *      class, uses, vertex flags, face normals: K37's definitions.  float64; every operation is rounded on its own, in the order written.
+ *
+ *   Definitions.
+ *     1. NEIGHBOURS.  N(i) = the other ends of the edges of K37's table that end at i, every class, each edge once however many faces use
+ *        it, in ascending vertex index: nbr_start (V + 1) int32, nbr_vertex (2 E) int32, nbr_edge (2 E) int32 (the edge's id).  One sort
+ *        of the 2 E keys (from << 32) | to gives all three.
+ *     2. WEIGHTS, per edge, from the input positions, kept through all iterations.  "uniform": w_e = 1.  "cotangent": for a valid face t and
+ *        k = 0, 1, 2 let P = t[(k + 2) % 3] (the corner opposite half-edge h = 3 t + k), Q = t[k], R = t[(k + 1) % 3]; u = Q - P, v = R - P;
+ *        d = (u_x v_x + u_y v_y) + u_z v_z; n = u x v (K36's cross); l = sqrt((n_x^2 + n_y^2) + n_z^2); cot_h = d / l if l > 0 and the
+ *        quotient is finite, else 0; 0 for half-edges of faces that are not valid.  w_e = the sum of cot_h over the edge's uses in
+ *        ascending h, starting from 0; then w_e = 0 unless w_e > 0 (negatives and NaN are clamped, which keeps every step a convex
+ *        combination of the vertex and its neighbours for a factor in (0, 1]).
+ *     3. LAPLACIAN of vertex i.  S = (0, 0, 0), W = 0; for j in N(i) in order: W = W + w_ij; S_a = S_a + w_ij (p_j,a - p_i,a).
+ *        delta_i,a = S_a / W if W > 0 and W is finite, else 0.
+ *     4. STEP with factor f.  q_i,a = p_i,a + f delta_i,a.  q_i = p_i, bit for bit, for a pinned vertex and for a vertex whose delta is 0 by
+ *        the "else" of (3) (no neighbours, or no positive weight: p + f 0 would turn a -0.0 into +0.0, and such a vertex is promised not to
+ *        move).  A step reads one buffer and writes another.
+ *     5. PINNED: the caller's mask, if any; with fix_boundary every vertex with K37's flag bit 1 (on a class-1 edge).  Unreferenced
+ *        vertices have no neighbours and never move.
+ *     6. SMOOTH (n, lambda, mu): n times a step with f = lambda, then, unless mu == 0, a step with f = mu.  mu == 0 is plain Laplacian
+ *        smoothing; lambda in (0, 1], mu in [-2, -lambda) is Taubin's (A signal processing approach to fair surface design, 1995).  n = 0
+ *        returns a copy.  The triangles are untouched.
+ *     7. DIHEDRAL ROUGHNESS per edge: for an edge of class 2 whose two uses' face normals n1, n2 (K37's unit normals) both have a non-zero
+ *        component, theta_e = atan2(sqrt(dot(c, c)), dot(n1, n2)) with c = n1 x n2 and K37's dot; NaN for every other edge.
+ *     Not here: re-projection onto the SDF's zero set, weights recomputed per iteration, implicit fairing, feature detection, volume
+ *     rescaling.
+ *
+ *   gens_mesh_corner_cot: per half-edge, cot (3 T) float64 by (2).
+ *   gens_mesh_edge_weights: per edge, one thread walks the edge's run [edge_start[e], edge_start[e + 1]) of halfedge_order (3 T) int32 --
+ *     K37's seg_start and order, the half-edges stably sorted by edge key -- and writes weight (E) float64 by (2).
+ *   gens_mesh_laplacian_step: per vertex, one thread walks [nbr_start[i], nbr_start[i + 1]) in order.  weight (E) float64 or NULL for
+ *     uniform; pinned (V) uint8 or NULL; n_neighbours = 2 E.  Writes out (V, 3) by (4) and, where given, delta (V, 3) by (3) and
+ *     weight_sum (V) (W); each of the three may be NULL, not all.  No atomics: deterministic.  None of the three may be `in` (neighbours
+ *     read it), and no two of them may be the same buffer; overlaps other than equal pointers are the caller's to avoid.
+ *   gens_mesh_dihedral: per edge, angle (E) float64 by (7) from K37's face_normal (T, 3), edge_halfedges (E, 2), edge_class (E).
+ *   Arguments are checked before any launch.  GENS_EINVAL: a negative count; more edges than half-edges; a half-edge count that is no
+ *     multiple of 3; n_neighbours != 2 E; a factor outside [-2, 1] or NaN; an output equal to `in` or to another output; no output; a null pointer that the given counts would
+ *     have the launch read or write.  GENS_ELIMIT: V, 3 T or 2 E >= 2^31.  Counts of zero succeed without a launch.  Ids outside their
+ *     ranges are skipped, never read through.  The ABI version stays 12: no existing entry changes.
+ * ---------------------------------------------------------------------------------------------------------- */
+int gens_mesh_corner_cot(const double* vertices, const int32_t* triangles, int64_t n_vertices, int64_t n_faces, double* cot, void* stream);
+int gens_mesh_edge_weights(const double* cot, const int32_t* edge_start, const int32_t* halfedge_order, int64_t n_edges, int64_t n_halfedges,
+                           double* weight, void* stream);
+int gens_mesh_laplacian_step(const double* in, int64_t n_vertices, const int32_t* nbr_start, const int32_t* nbr_vertex, const int32_t* nbr_edge,
+                             int64_t n_neighbours, const double* weight /* (E) or NULL */, int64_t n_edges, const uint8_t* pinned /* or NULL */,
+                             double factor, double* out /* (V, 3) or NULL */, double* delta /* (V, 3) or NULL */,
+                             double* weight_sum /* (V) or NULL */, void* stream);
+int gens_mesh_dihedral(const double* face_normal, int64_t n_faces, const int32_t* edge_halfedges, const uint8_t* edge_class, int64_t n_edges,
+                       double* angle, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K14  C (m x n) = A^T B for tall row-major operands A (k x m), B (k x n), k >> m, n: the weight-gradient product of the training
