@@ -129,7 +129,9 @@ def test_tv_levels_equal_the_per_level_kernels(dims):
 @pytest.mark.parametrize("nv", [3, 5])
 def test_fused_patch_warp_equals_the_operator_by_operator_mirror(nv):
     """gens_patch_warp_fwd / _bwd against projector.surface_patch_warp (the reference's tensor pipeline on the K9 reads, pinned to the
-    reference by golden g7): the same patches, and the same gradient with respect to the crossing depth."""
+    reference by golden g7): the same patches, and the same gradient with respect to the crossing depth.  This compares two float32 pipelines of
+    the project's own at one inside-only shape; the float64 pin of both of them, of the K9 reads and of the up-sampling lives in
+    tests/test_hip_patch_warp.py (reference and bounds: tests/patch_warp_reference.py, pinned on the CPU by test_patch_warp_reference_cpu.py)."""
     from gens_amd import ops, synthetic
     from gens_amd.models.modules.projector import surface_patch_warp
     sc = synthetic.make_scene(nv=nv, h=96, w=128, n_levels=3, seed=nv)
