@@ -373,7 +373,8 @@ def simplify_mesh(vertices, triangles, cell, origin=None, normals=None, colors=N
 @torch.no_grad()
 def compare_meshes(va, ta, vb, tb, device=None, **kw):
     """ops.mesh_distance (K36: exact point-to-triangle distances, both ways) for host meshes, numpy in like the cleaners: vertices (V,3),
-    triangles (F,3) of the meshes A and B (arrays or tensors); kw: ops.mesh_distance's density, samples, max_dist, signed -> its dict as plain
+    triangles (F,3) of the meshes A and B (arrays or tensors); kw: ops.mesh_distance's density, samples, max_dist, signed, sign, beta (sign="winding":
+    the sign from generalised winding numbers, K40, for meshes whose edges give K37 none) -> its dict as plain
     Python numbers (a_to_b / b_to_a with n, unmatched, mean, rms, max, q50, q90, q99 and, with signed=True, signed_mean, inside, no_sign (K37);
     hausdorff; chamfer; density_a, density_b).  ValueError for what
     ops.mesh_distance refuses, for triangle indices outside the vertices and for vertices that are not finite, before the device is
@@ -382,7 +383,7 @@ def compare_meshes(va, ta, vb, tb, device=None, **kw):
     unknown = sorted(set(kw) - set(ops.MESH_DISTANCE_KEYS))
     if unknown:
         raise ValueError(f"compare_meshes: unknown keyword {unknown[0]!r} (ops.mesh_distance's {', '.join(ops.MESH_DISTANCE_KEYS)})")
-    ops.mesh_distance_request("compare_meshes", **kw)
+    ops.mesh_distance_keywords("compare_meshes", kw)
     meshes = []
     for name, v, t in (("A", va, ta), ("B", vb, tb)):
         v_np = np.ascontiguousarray(as_numpy(v), dtype=np.float64).reshape(-1, 3)

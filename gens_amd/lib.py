@@ -81,6 +81,12 @@ class MeshShadeArgs(C.Structure):     # gens_mesh_shade_args (K35)
         (n, _p) for n in ("hit", "bary", "depth", "normal", "normal_img", "img", "seen")]
 
 
+class WindingPlanArgs(C.Structure):    # gens_winding_plan (K40)
+    _fields_ = [(n, _p) for n in ("vertices", "triangles", "face_order", "corners", "leaf_count", "leaf_area", "leaf_normal", "leaf_centre",
+                                  "leaf_radius2", "node_count", "node_area", "node_normal", "node_centre", "node_radius2")] + [
+        (n, _l) for n in ("n_vertices", "n_faces", "n_leaves", "n_nodes")]
+
+
 # name -> argtypes, mirroring include/gens_hip.h declaration by declaration
 SIGNATURES = {
     "gens_pack_nchw": [_p, _p, _i, _i, _i, _i, _p],
@@ -268,6 +274,8 @@ SIGNATURES = {
     "gens_mesh_edge_weights": [_p, _p, _p, _l, _l, _p, _p],
     "gens_mesh_laplacian_step": [_p, _l, _p, _p, _p, _l, _p, _l, _p, _d, _p, _p, _p, _p],
     "gens_mesh_dihedral": [_p, _l, _p, _p, _l, _p, _p],
+    "gens_mesh_winding_moments": [C.POINTER(WindingPlanArgs), _p],
+    "gens_mesh_winding_number": [C.POINTER(WindingPlanArgs), _p, _l, _d, _p, _p, _p],
 }
 
 _lib = None

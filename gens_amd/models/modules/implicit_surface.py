@@ -594,7 +594,7 @@ class ImplicitSurface(nn.Module):
             raise ValueError("simplify = True: pass the cell edge in lattice spacings (a positive number; None, False or 0: off)")
         return ops.simplify_request("simplify", simplify)[0]
 
-    mesh_simplify_error = None     # True or a dict of ops.mesh_distance's keywords (density, samples, max_dist): extract_geometry / validate measure the
+    mesh_simplify_error = None     # True or a dict of ops.mesh_distance's keywords (density, samples, max_dist, signed, sign, beta): extract_geometry / validate measure the
                                    # simplified mesh against the mesh it came from (K36) -> last_simplify_stats["error"].  None / False: off
 
     def _simplify_error_request(self, simplify_error, simplify):
@@ -611,7 +611,7 @@ class ImplicitSurface(nn.Module):
         unknown = sorted(set(simplify_error) - set(ops.MESH_DISTANCE_KEYS), key=str)
         if unknown:
             raise ValueError(f"simplify_error: unknown keyword {unknown[0]!r} (ops.mesh_distance's {', '.join(ops.MESH_DISTANCE_KEYS)})")
-        ops.mesh_distance_request("simplify_error", **simplify_error)
+        ops.mesh_distance_keywords("simplify_error", simplify_error)
         if simplify is None:
             raise ValueError("simplify_error measures the simplified mesh against the extracted one: it needs simplify (a cell edge in lattice spacings)")
         return dict(simplify_error)

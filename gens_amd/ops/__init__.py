@@ -34,6 +34,7 @@ is what it was when ops was one module:
     ops.mesh_topology  K37: the edge table of a mesh, its topology report, pseudonormals (mesh_topology) and the signed distance (signed_distance_to_mesh).
     ops.mesh_repair  K38: mesh repair: duplicate faces, pinches and non-manifold edges split, small components, orientation, small holes (repair_mesh).
     ops.mesh_fairing  K39: mesh fairing: Laplacian / Taubin smoothing with uniform or cotangent weights (smooth_mesh), mesh_laplacian, mesh_roughness.
+    ops.winding   K40: generalised winding numbers, exact or with a bounded far field (build_winding_plan, winding_number), and the inside test (mesh_inside).
 """
 from .base import *  # noqa: F401,F403
 from .volume import *  # noqa: F401,F403
@@ -56,6 +57,7 @@ from .fusion import *  # noqa: F401,F403
 from .simplify import *  # noqa: F401,F403
 from .texture import *  # noqa: F401,F403
 from .mesh_render import *  # noqa: F401,F403
+from .winding import *  # noqa: F401,F403
 from .mesh_distance import *  # noqa: F401,F403
 from .mesh_topology import *  # noqa: F401,F403
 from .mesh_repair import *  # noqa: F401,F403

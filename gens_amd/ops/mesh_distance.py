@@ -8,10 +8,12 @@ import ctypes as C
 from .base import *  # noqa: F401,F403
 from .geometry import MeshGrid, build_mesh_grid
 from .points import sample_mesh_points
+from .winding import build_winding_plan, mesh_inside, mesh_sign_request, winding_sign
 
 _f64, _i32, _u8 = torch.float64, torch.int32, torch.uint8
 MESH_DISTANCE_SAMPLES = 1_000_000
-MESH_DISTANCE_KEYS = ("density", "samples", "max_dist", "signed")      # what extract_geometry(simplify_error=dict) may name
+MESH_DISTANCE_KEYS = ("density", "samples", "max_dist", "signed", "sign", "beta")      # what extract_geometry(simplify_error=dict) may name
+WINDING_SIGN_CHUNK = 1 << 18         # queries per K40 launch of mesh_distance(sign="winding"): no launch holds the device for long
 NO_REGION = 255                                                # the region code of a query without a face
 
 distance_section_hook = None         # a callable(name), called where a part of mesh_distance begins (scripts/mesh_distance_bench.py records HIP events there)
@@ -149,7 +151,15 @@ def mesh_distance_request(who, density=None, samples=MESH_DISTANCE_SAMPLES, max_
     return density, samples, distance_cap(who, max_dist)
 
 
-def mesh_distance(va, ta, vb, tb, density=None, samples=MESH_DISTANCE_SAMPLES, max_dist=float("inf"), return_samples=False, signed=False):
+def mesh_distance_keywords(who, kw):
+    """A dict of mesh_distance's keywords (MESH_DISTANCE_KEYS), checked on the host: mesh_distance_request for the first four,
+    mesh_sign_request for `sign` and `beta`.  ValueError for what either refuses."""
+    mesh_distance_request(who, **{k: v for k, v in kw.items() if k not in ("sign", "beta")})
+    mesh_sign_request(who, kw.get("signed", False), kw.get("sign", "pseudonormal"), kw.get("beta", None))
+
+
+def mesh_distance(va, ta, vb, tb, density=None, samples=MESH_DISTANCE_SAMPLES, max_dist=float("inf"), return_samples=False, signed=False,
+                  sign="pseudonormal", beta=None):
     """The two-sided distance between the meshes A = (va, ta) and B = (vb, tb): vertices (V, 3) float64 and triangles (T, 3) int32 on the
     device.  Each mesh is sampled with ops.sample_mesh_points -- ALL its vertices, then K24's lattice points at spacing `density` (the DTU
     score's sampler; the vertices come on top of the area-uniform lattice, so regions of small triangles weigh more: on a mesh whose
@@ -166,7 +176,10 @@ def mesh_distance(va, ta, vb, tb, density=None, samples=MESH_DISTANCE_SAMPLES, m
     orientation gives it (ops.signed_distance_to_mesh: positive on the side its face normals point to) and a direction gains signed_mean
     (the mean over the matched samples that have a sign; NaN if none has), inside (the count of negative ones) and no_sign (matched samples
     whose closest point has no sign: on a boundary, flipped or non-manifold edge, a pinched vertex, a degenerate face); with return_samples
-    also "signed_a" / "signed_b".  ValueError before any launch for what closest_point_on_mesh, build_mesh_grid's inputs and the keywords exclude."""
+    also "signed_a" / "signed_b".  sign="winding" (K40; needs signed=True) takes the sign from the OTHER mesh's generalised winding number
+    instead (ops.mesh_inside with `beta`, default MESH_DISTANCE_BETA): negative where the sample is inside, whatever the mesh's edges are
+    like -- open, pinched, folded, a soup --, the same three keys, no_sign now counting the samples the far field's bound leaves undecided;
+    an inside-out mesh has nothing inside it (ops.repair_mesh re-orients).  ValueError before any launch for what closest_point_on_mesh, build_mesh_grid's inputs and the keywords exclude."""
     who = "mesh_distance"
     for name, t, dtype in (("va", va, _f64), ("ta", ta, _i32), ("vb", vb, _f64), ("tb", tb, _i32)):
         if not torch.is_tensor(t) or not t.is_cuda:
@@ -176,6 +189,8 @@ def mesh_distance(va, ta, vb, tb, density=None, samples=MESH_DISTANCE_SAMPLES, m
         if t.device != va.device:
             raise ValueError(f"{who}: va on {va.device}, {name} on {t.device}")
     density, samples, cap = mesh_distance_request(who, density, samples, max_dist, signed)
+    sign, beta = mesh_sign_request(who, signed, sign, beta)
+    pseudo = signed and sign == "pseudonormal"
     _distance_section("grids")
     meshes = [(_c(va.detach()), _c(ta.detach())), (_c(vb.detach()), _c(tb.detach()))]
     grids = [build_mesh_grid(v, t) for v, t in meshes]
@@ -191,9 +206,13 @@ def mesh_distance(va, ta, vb, tb, density=None, samples=MESH_DISTANCE_SAMPLES, m
     results = []
     for k in (0, 1):
         _distance_section("query_a_to_b" if k == 0 else "query_b_to_a")
-        results.append(mesh_closest_dist2(points[k], grids[1 - k], cap, signed, signed))
+        results.append(mesh_closest_dist2(points[k], grids[1 - k], cap, pseudo, pseudo))
     signs = None
-    if signed:
+    if signed and not pseudo:
+        _distance_section("sign")
+        signs = [winding_sign(results[k][0], mesh_inside(points[k], build_winding_plan(*meshes[1 - k]), beta, WINDING_SIGN_CHUNK, who=who))
+                 for k in (0, 1)]
+    elif signed:
         from .mesh_topology import distance_sign, mesh_topology
         _distance_section("sign")
         signs = [distance_sign(points[k], *results[k], mesh_topology(*meshes[1 - k], normals=True)) for k in (0, 1)]

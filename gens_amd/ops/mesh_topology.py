@@ -7,6 +7,7 @@ Part of gens_amd.ops (see ops/__init__.py)."""
 from .base import *  # noqa: F401,F403
 from .geometry import MeshGrid, face_components
 from .mesh_distance import mesh_closest_dist2
+from .winding import WINDING_SIGNS, WindingPlan, mesh_inside, winding_beta, winding_sign
 
 _f64, _i32, _i64, _u8 = torch.float64, torch.int32, torch.int64, torch.uint8
 EDGE_BOUNDARY, EDGE_MANIFOLD, EDGE_FLIPPED, EDGE_NONMANIFOLD = 1, 2, 3, 4
@@ -236,7 +237,24 @@ def distance_sign(queries, dist2, face, point, region, topology):
     return signed
 
 
-def signed_distance_to_mesh(queries, grid, topology, max_dist=float("inf"), chunk=None):
+def _winding_signed_distance(who, queries, grid, winding, beta, max_dist, chunk):
+    """signed_distance_to_mesh's sign="winding" route: K36's distance, K40's inside test."""
+    if not isinstance(grid, MeshGrid):
+        raise ValueError(f"{who}: grid is {type(grid).__name__}, expected ops.build_mesh_grid's MeshGrid")
+    if not isinstance(winding, WindingPlan):
+        raise ValueError(f"{who}: winding is {type(winding).__name__}, expected ops.build_winding_plan's WindingPlan of the grid's mesh "
+                         f"(sign=\"winding\" takes its sign from it)")
+    if winding.n_vertices != grid.vertices.shape[0] or winding.n_faces != grid.n_faces:
+        raise ValueError(f"{who}: the winding plan is of another mesh ({winding.n_vertices} vertices, {winding.n_faces} faces; the grid's mesh "
+                         f"has {grid.vertices.shape[0]} and {grid.n_faces})")
+    if winding.vertices.device != grid.vertices.device:
+        raise ValueError(f"{who}: the winding plan on {winding.vertices.device}, the grid on {grid.vertices.device}")
+    winding_beta(who, beta)
+    dist2, face, _, _ = mesh_closest_dist2(queries, grid, max_dist, False, False, chunk)
+    return winding_sign(dist2, mesh_inside(queries, winding, beta, chunk, who=who)), face
+
+
+def signed_distance_to_mesh(queries, grid, topology=None, max_dist=float("inf"), chunk=None, sign="pseudonormal", winding=None, beta=None):
     """K36's distance with K37's sign.  queries (n, 3) float64 on the device, grid = ops.build_mesh_grid(vertices, triangles), topology =
     ops.mesh_topology(vertices, triangles, normals=True) of the same mesh -> (signed (n) float64, face (n) int32).  |signed| is
     closest_point_on_mesh's distance; the sign is that of (q - closest point) . n with n the face normal, or the angle-weighted vertex
@@ -244,8 +262,20 @@ def signed_distance_to_mesh(queries, grid, topology, max_dist=float("inf"), chun
     point to, so negative inside a mesh whose normals point outwards.  Exact for a watertight mesh.  +0 on the mesh.
     NaN where there is no sign: nothing within max_dist, a closest point on a boundary, flipped or non-manifold edge or on a vertex of
     such an edge or a pinched one, a degenerate closest face, a query at right angles to the normal.  One K36 launch per chunk and one sign
-    launch.  ValueError before any launch for what closest_point_on_mesh refuses, a topology without normals or of another mesh."""
+    launch.  sign="winding" (K40; the default route issues not one more launch and is what it was, bit for bit): the sign comes from the
+    generalised winding number instead -- winding = ops.build_winding_plan(vertices, triangles) of the same mesh, beta as ops.mesh_inside
+    takes it (None: exact), `topology` is not needed -- -d where mesh_inside says 1, +d where it says 0, NaN where it is undecided or
+    nothing lies within max_dist, +0 on the mesh.  It has a sign where K37 has none (a closest point on a rim, a pinch, a fold; a soup) and
+    says whether the query is inside the OBJECT, not on which side of the nearest sheet it lies; inside an inside-out mesh nothing is
+    (ops.repair_mesh re-orients).  ValueError before any launch for what closest_point_on_mesh refuses, a topology without normals or of
+    another mesh, a sign that is neither name, a winding plan or beta without sign="winding", a plan of another mesh, a bad beta."""
     who = "signed_distance_to_mesh"
+    if sign not in WINDING_SIGNS:
+        raise ValueError(f"{who}: sign = {sign!r}: one of {', '.join(WINDING_SIGNS)}")
+    if sign == "winding":
+        return _winding_signed_distance(who, queries, grid, winding, beta, max_dist, chunk)
+    if winding is not None or beta is not None:
+        raise ValueError(f"{who}: winding and beta go with sign=\"winding\"")
     _check_sign_topology(who, grid, topology)
     dist2, face, point, region = mesh_closest_dist2(queries, grid, max_dist, True, True, chunk)
     return distance_sign(_c(queries.detach()), dist2, face, point, region, topology), face

@@ -72,7 +72,8 @@ const char* gens_last_error(void);
  *       gens_texture_pack, gens_texture_uv, and K35's gens_mesh_shade, and K36's gens_mesh_closest_point, and K37's gens_mesh_edge_keys,
  *       gens_mesh_edge_classify, gens_mesh_fan_pairs, gens_mesh_vertex_classify, gens_mesh_pseudonormals, gens_mesh_distance_sign, and K38's
  *       gens_mesh_face_keys, gens_mesh_split_corners, gens_mesh_orient_pairs, gens_mesh_apply_flips, gens_mesh_loop_centroids,
- *       gens_mesh_fill_emit, and K39's gens_mesh_corner_cot, gens_mesh_edge_weights, gens_mesh_laplacian_step, gens_mesh_dihedral. */
+ *       gens_mesh_fill_emit, and K39's gens_mesh_corner_cot, gens_mesh_edge_weights, gens_mesh_laplacian_step, gens_mesh_dihedral, and K40's
+ *       gens_mesh_winding_moments, gens_mesh_winding_number. */
 int gens_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -1541,6 +1542,79 @@ int gens_mesh_laplacian_step(const double* in, int64_t n_vertices, const int32_t
                              double* weight_sum /* (V) or NULL */, void* stream);
 int gens_mesh_dihedral(const double* face_normal, int64_t n_faces, const int32_t* edge_halfedges, const uint8_t* edge_class, int64_t n_edges,
                        double* angle, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * K40  Generalised winding numbers (Jacobson, Kavan, Sorkine-Hornung: Robust inside-outside segmentation using generalized winding
+ *      numbers, 2013), exact and with a far field over clusters (after Barill et al.: Fast winding numbers for soups and clouds, 2018,
+ *      first order only): an inside test that needs no connectivity (ops.build_winding_plan, ops.winding_number, ops.mesh_inside,
+ *      ops.signed_distance_to_mesh(sign="winding"), ops.mesh_distance(sign="winding"), io.compare_meshes(sign=),
+ *      python -m gens_amd.compare_meshes --signed --sign winding), csrc/k40_mesh_winding.hip.  tests/winding_reference.py restates all of
+ *      it in numpy.  vertices (V, 3) float64, triangles (T, 3) int32; V < 2^31 and 3 T < 2^31.  VALID: K37's rule (three different
+ *      indices, all in [0, V)).  float64; every operation is rounded on its own, in the order written; dot(u, v) = (u_x v_x + u_y v_y) +
+ *      u_z v_z, |u| = sqrt(dot(u, u)), cross as in K36.
+ *
+ *   Definitions.
+ *     1. SOLID ANGLE of a valid face (a, b, c) at the query q (Van Oosterom and Strackee, 1983): A = a - q, B = b - q, C = c - q;
+ *        num = dot(A, B x C); den = (((|A| |B|) |C| + dot(A, B) |C|) + dot(B, C) |A|) + dot(C, A) |B|; Omega = 2 atan2(num, den).  A face
+ *        that is not valid adds nothing.  A query on a vertex or in the plane of a face gets what the formula gives, which is finite
+ *        (atan2(+-0, x) is +-0 or +-pi): on a face the face counts as 0, or as +-2 pi where den < 0 -- half of the jump across it --; nothing
+ *        is special-cased.
+ *     2. w(q) = (the sum of Omega over the faces) / (4 pi): 1 inside a closed mesh whose normals point outwards, 0 outside, -1 inside an
+ *        inside-out mesh (which therefore reads as "outside everywhere": repair_mesh re-orients), k where k sheets enclose q, a smooth
+ *        fraction near a hole.  NaN for a query with a coordinate that is not finite.
+ *     3. PLAN ORDER.  face_order (T) int32: the faces stably sorted by the Morton key of their centroid ((a + b) + c) / 3 -- 10 bits per
+ *        axis over the bounding box of the valid faces' centroids, x the most significant of each triple; faces that are not valid last --
+ *        ties by face index.  LEAF l = the faces at positions 64 l .. 64 l + 63 of that order, NODE k = the leaves 64 k .. 64 k + 63.  Any
+ *        permutation of the faces is a correct plan (the order only decides how tight the clusters are); the kernels take it as given.
+ *     4. MOMENTS of a leaf, over its valid faces in position order, sums starting from 0: with n_f = (b - a) x (c - a), a_f = 0.5 |n_f|,
+ *        g_f = ((a + b) + c) / 3:  count; area = sum a_f; normal = sum 0.5 n_f; S = sum a_f g_f; M = sum g_f; centre p = S / area if
+ *        area > 0, else M / count; radius2 = max over the faces' corners v of dot(v - p, v - p).  A leaf with count 0 is EMPTY: zeros, and
+ *        it is skipped everywhere.  Of a node, over its leaves that are not empty in order: count = sum count_l; area = sum area_l;
+ *        normal = sum normal_l; S = sum area_l p_l; M = sum count_l p_l; p as above; r = max (|p_l - p| + sqrt(radius2_l)), which is no
+ *        smaller than the distance from p to any corner; radius2 = r r.
+ *     5. FAR FIELD of a cluster (leaf or node) with area, normal N, centre p, radius2 for the query q and beta2 = beta beta:
+ *        D = p - q, d2 = dot(D, D).  The cluster is ACCEPTED if d2 > beta2 radius2.  Then d = sqrt(d2), r = sqrt(radius2) and it stands for
+ *        the solid angle  dot(N, D) / (d2 d)  with an error of at most  err = (area r) / (2 pi ((g g) g)), g = d - r, in units of w:
+ *        w is the integral of g(y - q) . n over the surface with g(y) = y / (4 pi |y|^3), whose Jacobian I / (4 pi |y|^3) - 3 y y^T /
+ *        (4 pi |y|^5) has eigenvalues 1 / (4 pi |y|^3) (twice) and -2 / (4 pi |y|^3), so an operator norm of 1 / (2 pi |y|^3); every
+ *        point y of the cluster is within r of p and at least d - r from q, so |g(y - q) - g(p - q)| <= r / (2 pi (d - r)^3), and the
+ *        integral of that over the cluster's area is err.  (The dipole replaces g(y - q) by g(p - q) and the integral of n is N.)
+ *     6. TRAVERSAL.  total = 0, bound = 0.  For each node k that is not empty, in order: if beta > 0 and the node is accepted: part = its
+ *        dipole, bound = bound + err.  Else part = 0 and for each of its leaves l that is not empty, in order: if beta > 0 and the leaf is
+ *        accepted: leaf = its dipole, bound = bound + err; else leaf = 0 and, for its faces in position order, leaf = leaf + Omega;
+ *        then part = part + leaf.  Then total = total + part.  w = total / (4 pi).  beta = 0 accepts nothing: the exact sum, in this
+ *        tree's order, and bound = 0.  |w(beta) - w(0)| <= bound up to rounding.  The tree is fixed and a query's sums are its own: its
+ *        bits do not depend on the other queries of the call, their number, or the run.
+ *     Not here: expansion terms beyond the dipole, a deeper tree, sorting the queries, splitting one query's nodes over workgroups,
+ *     orientation guessing, self-intersection tests, voxelisation.
+ *
+ *   gens_winding_plan: the mesh (read by gens_mesh_winding_moments only), face_order, and what the moments launch writes and the query
+ *     reads: corners (64 L, 9) float64 -- a, b, c of the face at each position, NINE ZEROS for a face that is not valid or a position
+ *     past T (the solid angle of such a triple is +-0 at every query: it adds nothing) --, and per leaf (L = ceil(T / 64)) and per node
+ *     (K = ceil(L / 64)) count int32, area, normal (, 3), centre (, 3), radius2 float64.
+ *   gens_mesh_winding_moments: one thread per leaf, then one per node (4).  Indices in face_order and triangles outside their ranges
+ *     make the face not valid; they are never read through.
+ *   gens_mesh_winding_number: one query per lane; queries (n, 3) float64 -> w (n) and, unless NULL, bound (n) (NaN where w is).
+ *     beta = 0: exact; else a finite number > 1 (so that d > r in (5)).  Reads the plan's corners and moments only.
+ *   Arguments are checked before any launch.  GENS_EINVAL: a null plan; a negative count; leaf or node counts that are not the ceilings
+ *     above; beta that is neither 0 nor a finite number > 1; two of queries, w, bound equal; a null pointer that the counts would have a
+ *     launch read or write.  GENS_ELIMIT: V, 3 T or n >= 2^31.  T = 0: moments launch nothing, the query writes 0 (NaN).  n = 0 succeeds
+ *     without a launch.  The ABI version stays 12: no existing entry changes.
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct {
+    const double* vertices;      /* (V, 3) */
+    const int32_t* triangles;    /* (T, 3) */
+    const int32_t* face_order;   /* (T) */
+    double* corners;             /* (64 L, 9) */
+    int32_t* leaf_count;         /* (L) */
+    double *leaf_area, *leaf_normal, *leaf_centre, *leaf_radius2;      /* (L), (L, 3), (L, 3), (L) */
+    int32_t* node_count;         /* (K) */
+    double *node_area, *node_normal, *node_centre, *node_radius2;      /* (K), (K, 3), (K, 3), (K) */
+    int64_t n_vertices, n_faces, n_leaves, n_nodes;
+} gens_winding_plan;
+int gens_mesh_winding_moments(const gens_winding_plan* plan, void* stream);
+int gens_mesh_winding_number(const gens_winding_plan* plan, const double* queries, int64_t n_queries, double beta, double* w,
+                             double* bound /* (n) or NULL */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K14  C (m x n) = A^T B for tall row-major operands A (k x m), B (k x n), k >> m, n: the weight-gradient product of the training
