@@ -402,17 +402,26 @@ def compare_meshes(va, ta, vb, tb, device=None, **kw):
 
 
 @torch.no_grad()
-def mesh_report(vertices, triangles, device=None, roughness=False):
+def mesh_report(vertices, triangles, device=None, roughness=False, self_intersections=False, max_pairs=None):
     """ops.mesh_topology(...).report() (K37) for a host mesh, numpy in like the cleaners: vertices (V,3), triangles (F,3) (arrays or tensors)
     -> the dict of Python numbers: vertices, vertices_referenced, faces, faces_invalid, edges and their counts by class (boundary, manifold,
     flipped, non-manifold), vertices_pinched, vertices_nonmanifold, components, largest_component_faces, boundary_components, euler, closed,
     oriented, manifold, watertight, genus (None unless watertight), area, volume.  Any indices are accepted: a face with an index outside
     the vertices or a repeated one is counted as invalid and takes part in nothing else.  roughness=True: a further key "roughness", ops.
-    mesh_roughness's report {edges, mean, rms, max} of the dihedral angles (K39).  ValueError, before the device is looked at, for arrays
-    that are not (n, 3), indices that are not whole numbers or do not fit int32, a `roughness` that is no bool."""
+    mesh_roughness's report {edges, mean, rms, max} of the dihedral angles (K39).  self_intersections=True: a further key
+    "self_intersections", the counts of ops.mesh_self_intersections (K41: candidates, intersecting and undecided pairs, degenerate and
+    uncertain faces, ...); with max_pairs=N also "pairs": {"pairs": the first N (s, t), "kinds": 1 intersecting / 2 undecided}.  The
+    defaults launch nothing of K41 and return what they did.  ValueError, before the device is looked at, for arrays that are not (n, 3),
+    indices that are not whole numbers or do not fit int32, a `roughness` or `self_intersections` that is no bool, a max_pairs that is no
+    positive int or None, or that comes without self_intersections=True."""
     from . import ops
     if not isinstance(roughness, bool):
         raise ValueError(f"mesh_report: roughness = {roughness!r}: True or False")
+    if not isinstance(self_intersections, bool):
+        raise ValueError(f"mesh_report: self_intersections = {self_intersections!r}: True or False")
+    ops.check_intersect_request("mesh_report", True, max_pairs)
+    if max_pairs is not None and not self_intersections:
+        raise ValueError("mesh_report: max_pairs goes with self_intersections=True")
     v_np, t_np = np.asarray(as_numpy(vertices)), np.asarray(as_numpy(triangles))
     if any(x.size and (x.ndim != 2 or x.shape[1] != 3) for x in (v_np, t_np)):
         raise ValueError(f"mesh_report: vertices {v_np.shape}, triangles {t_np.shape}: expected (V, 3) and (F, 3)")
@@ -423,11 +432,21 @@ def mesh_report(vertices, triangles, device=None, roughness=False):
     v_np = np.ascontiguousarray(v_np, dtype=np.float64).reshape(-1, 3)
     t_np = np.ascontiguousarray(t_np.reshape(-1, 3), dtype=np.int32)
     dev = device_of(vertices, triangles, device=device)
-    if not roughness:
+    if not roughness and not self_intersections:
         return ops.mesh_topology(torch.from_numpy(v_np).to(dev), torch.from_numpy(t_np).to(dev)).report()
     dv, dt = torch.from_numpy(v_np).to(dev), torch.from_numpy(t_np).to(dev)
-    topo = ops.mesh_topology(dv, dt, normals=True)
-    return {**topo.report(), "roughness": ops.mesh_roughness(dv, dt, topology=topo)[1]}
+    topo = ops.mesh_topology(dv, dt, normals=roughness)
+    out = topo.report()
+    if roughness:
+        out["roughness"] = ops.mesh_roughness(dv, dt, topology=topo)[1]
+    if self_intersections:
+        if max_pairs is None:
+            out["self_intersections"] = ops.self_intersection_counts(dv, dt, who="mesh_report")
+        else:
+            found = ops.self_intersections_of(dv, dt, max_pairs=max_pairs, who="mesh_report")
+            out["self_intersections"] = {k: found.counts[k] for k in ops.SELF_INTERSECTION_KEYS}
+            out["pairs"] = {"pairs": found.pairs.cpu().tolist(), "kinds": found.kinds.cpu().tolist()}
+    return out
 
 
 def _mesh_arrays(who, vertices, triangles):

@@ -276,6 +276,9 @@ SIGNATURES = {
     "gens_mesh_dihedral": [_p, _l, _p, _p, _l, _p, _p],
     "gens_mesh_winding_moments": [C.POINTER(WindingPlanArgs), _p],
     "gens_mesh_winding_number": [C.POINTER(WindingPlanArgs), _p, _l, _d, _p, _p, _p],
+    "gens_mesh_isect_faces": [_p, _l, _p, _l, _p, _p, _p],
+    "gens_mesh_isect_count": [C.POINTER(MeshGridArgs), _l, _l, _l, _p, _p, _p, _p, _p, _p],
+    "gens_mesh_isect_emit": [C.POINTER(MeshGridArgs), _l, _l, _l, _p, _p, _p, _p, _l, _p, _p, _p],
 }
 
 _lib = None

@@ -115,6 +115,9 @@ class GenS(nn.Module):
         topology = confs.get("mesh_topology", None)             # optional: ... and take the topology report of the returned mesh (ops.mesh_topology, K37); True
         if topology is not None:
             self.implicit_surface.mesh_topology = bool(topology)
+        crossing = confs.get("mesh_self_intersections", None)   # optional: ... and count the self-intersections of the returned mesh (ops.mesh_self_intersections, K41); True
+        if crossing is not None:
+            self.implicit_surface.mesh_self_intersections = bool(crossing)
         repair = confs.get("mesh_repair", None)                 # optional: ... and repair the mesh on the device before that report, the attributes and the texture (ops.repair_mesh, K38); True or a dict of its keywords
         if repair is not None:
             self.implicit_surface.mesh_repair = repair if isinstance(repair, bool) else dict(repair)

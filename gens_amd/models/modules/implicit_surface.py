@@ -620,6 +620,20 @@ class ImplicitSurface(nn.Module):
                                    # last_mesh_topology.  None / False: off
     last_mesh_topology = None      # ops.MeshTopology.report() of the mesh the last extract_geometry call returned (None: that call did not ask)
 
+    mesh_self_intersections = None       # True: extract_geometry / validate count the self-intersections of the mesh they return (ops.mesh_self_
+                                         # intersections, K41) -> last_mesh_self_intersections.  None / False: off
+    last_mesh_self_intersections = None  # the counts dict for the mesh the last extract_geometry call returned (None: that call did not ask)
+
+    def _self_intersections_request(self, self_intersections):
+        """The self-intersection report a mesh call asks for (None: the attribute `mesh_self_intersections`) -> bool.  ValueError for anything
+        but None or a bool."""
+        asked = self.mesh_self_intersections if self_intersections is None else self_intersections
+        if asked is None:
+            return False
+        if not isinstance(asked, bool):
+            raise ValueError(f"self_intersections = {asked!r}: True (None or False: off)")
+        return asked
+
     def _topology_request(self, topology):
         """The topology report a mesh call asks for (None: the attribute `mesh_topology`) -> bool.  ValueError for anything but None or a bool."""
         topology = self.mesh_topology if topology is None else topology
@@ -1269,7 +1283,8 @@ class ImplicitSurface(nn.Module):
         return out
 
     def extract_geometry(self, volumes, bound_min, bound_max, resolution, threshold, shard=None, sparse=None, sparse_mesh=None, attributes=None,
-                         views=None, simplify=None, texture=None, simplify_error=None, topology=None, repair=None, smooth=None):
+                         views=None, simplify=None, texture=None, simplify_error=None, topology=None, repair=None, smooth=None,
+                         self_intersections=None):
         """-> vertices (V,3) float64, triangles (T,3) int32 as numpy arrays (implicit_surface.py:407-427).  The SDF lattice and
         the marching cubes both run on the device (the reference: 512 D2H copies + PyMCubes on the host); only the mesh is copied.
         sparse: sdf_grid's option of that name, with this call's threshold.  sparse_mesh (default: the attribute of that name, None = off):
@@ -1300,6 +1315,12 @@ class ImplicitSurface(nn.Module):
         device-resident mesh after the simplification and before the read-back, on every route; with simplify also on,
         self.last_simplify_stats["topology_before"] holds the report of the mesh before it.  Off: nothing is launched and
         last_mesh_topology is None.  ValueError before any launch for another value.
+        self_intersections (default: the attribute `mesh_self_intersections`; None or False = off): True -> self.last_mesh_self_intersections
+        holds the counts of ops.mesh_self_intersections for the mesh this call returns (K41: candidate pairs of faces, how many intersect,
+        how many are undecided, degenerate and uncertain faces), taken where the topology report is taken, after
+        simplify / repair / smooth; with simplify, repair or smooth on, that stage's stats also hold "self_intersections_before", the
+        counts of the mesh before it, so a stage that introduces intersections shows it.  Off: nothing is launched and
+        last_mesh_self_intersections is None.  ValueError before any launch for another value.
         repair (default: the attribute `mesh_repair`; None or False = off): True, or a dict of ops.repair_mesh's keywords (split, orient,
         min_component_faces, max_hole_edges, dedupe).  The device-resident mesh is repaired (K38: duplicate faces dropped, pinches and
         non-manifold edges split, small components dropped, components re-oriented, small holes closed) after the simplification and its
@@ -1324,6 +1345,7 @@ class ImplicitSurface(nn.Module):
         simplify = self._simplify_request(simplify)
         simplify_error = self._simplify_error_request(simplify_error, simplify)
         topology = self._topology_request(topology)
+        self_intersections = self._self_intersections_request(self_intersections)
         repair = self._repair_request(repair)
         smooth = self._smooth_request(smooth)
         texture = self._texture_option(texture)
@@ -1332,6 +1354,7 @@ class ImplicitSurface(nn.Module):
             self._texture_request(None, volumes, views, *(texture.get(k, d) for k, d in (("texels", 8), ("snap", 0), ("max_move", None))))
         self.last_simplify_stats = None
         self.last_mesh_topology = None
+        self.last_mesh_self_intersections = None
         self.last_repair_stats = None
         self.last_smooth_stats = None
         route, brick = self._lattice_route(sparse, sparse_mesh, shard)
@@ -1352,21 +1375,32 @@ class ImplicitSurface(nn.Module):
         if simplify is not None:
             full = (vertices, triangles) if simplify_error is not None else None
             before = ops.mesh_topology(vertices, triangles).report() if topology else None
+            crossing = ops.self_intersection_counts(vertices, triangles) if self_intersections else None
             vertices, triangles, _, self.last_simplify_stats = ops.simplify_mesh(vertices, triangles, simplify, origin=(-0.5, -0.5, -0.5))
             if before is not None:
                 self.last_simplify_stats["topology_before"] = before
+            if crossing is not None:
+                self.last_simplify_stats["self_intersections_before"] = crossing
             if full is not None:
                 self.last_simplify_stats["error"] = ops.mesh_distance(*full, vertices, triangles, **simplify_error)
                 del full
         if repair is not None:
             before = ops.mesh_topology(vertices, triangles).report() if topology else None
+            crossing = ops.self_intersection_counts(vertices, triangles) if self_intersections else None
             vertices, triangles, _, _, _, self.last_repair_stats = ops.repair_mesh(vertices, triangles, **repair)
             if before is not None:
                 self.last_repair_stats["topology_before"] = before
+            if crossing is not None:
+                self.last_repair_stats["self_intersections_before"] = crossing
         if smooth is not None:
+            crossing = ops.self_intersection_counts(vertices, triangles) if self_intersections else None
             vertices, triangles, self.last_smooth_stats = ops.smooth_mesh(vertices, triangles, **smooth)
+            if crossing is not None:
+                self.last_smooth_stats["self_intersections_before"] = crossing
         if topology:
             self.last_mesh_topology = ops.mesh_topology(vertices, triangles).report()
+        if self_intersections:
+            self.last_mesh_self_intersections = ops.self_intersection_counts(vertices, triangles)
         b_max, b_min = bound_max.detach().cpu().numpy(), bound_min.detach().cpu().numpy()
         attrs = tex = None
         if attributes or texture is not None:          # on the device-resident vertices; span: the host expression's (float32) difference, widened
@@ -1385,7 +1419,8 @@ class ImplicitSurface(nn.Module):
     def validate(self, rays_o, rays_d, near, far, volumes, mask_volumes, imgs, features, match_features, intrs, c2ws, bound_min, bound_max,
                  hw, cos_anneal_ratio=1.0, step=None, extract_geometry=True, mesh_resolution=512, threshold=0.0, scene=None, shard=None, sparse=None,
                  sparse_mesh=None, mesh_attributes=None, surface_render=None, surface_fusion=None, mesh_simplify=None, mesh_texture=None,
-                 mesh_render=None, mesh_simplify_error=None, mesh_topology=None, mesh_repair=None, mesh_smooth=None):
+                 mesh_render=None, mesh_simplify_error=None, mesh_topology=None, mesh_repair=None, mesh_smooth=None,
+                 mesh_self_intersections=None):
         """shard (gens_amd.distributed.Shard, optional): render only this rank's contiguous ray range and evaluate only its lattice
         chunks; the (P, 8) image buffer / the lattice slabs are gathered over RCCL, so every rank returns the whole image.  The jitter
         of EVERY ray is drawn on every rank from the identically seeded CPU generator (the reference's draw order) and sliced with
@@ -1402,7 +1437,9 @@ class ImplicitSurface(nn.Module):
         `simplify_error` (True or a dict of ops.mesh_distance's keywords; default: the attribute of that name, None / False = off): the
         simplified mesh is measured against the extracted one (K36) into self.last_simplify_stats["error"]; ValueError before any launch
         when the simplification is off.  mesh_topology: extract_geometry's `topology` (True; default: the attribute of that name, None /
-        False = off): self.last_mesh_topology holds the topology report of the returned mesh (K37).  mesh_repair: extract_geometry's `repair`
+        False = off): self.last_mesh_topology holds the topology report of the returned mesh (K37).  mesh_self_intersections: extract_geometry's
+        `self_intersections` (True; default: the attribute of that name, None / False = off): self.last_mesh_self_intersections holds the
+        self-intersection counts of the returned mesh (K41).  mesh_repair: extract_geometry's `repair`
         (True or a dict of ops.repair_mesh's keywords; default: the attribute of that name, None / False = off): the mesh is repaired on the
         device (K38) before the report, the attributes and the texture; self.last_repair_stats holds its counts.  mesh_smooth: extract_geometry's
         `smooth` (True or a dict of ops.smooth_mesh's keywords; default: the attribute of that name, None / False = off): the mesh is smoothed
@@ -1427,6 +1464,7 @@ class ImplicitSurface(nn.Module):
         mesh_simplify = self._simplify_request(mesh_simplify) if extract_geometry else None      # (refused before anything is launched)
         mesh_simplify_error = self._simplify_error_request(mesh_simplify_error, mesh_simplify) if extract_geometry else None
         mesh_topology = self._topology_request(mesh_topology) if extract_geometry else False
+        mesh_self_intersections = self._self_intersections_request(mesh_self_intersections) if extract_geometry else False
         mesh_repair = self._repair_request(mesh_repair) if extract_geometry else None
         mesh_smooth = self._smooth_request(mesh_smooth) if extract_geometry else None
         mesh_texture = self._texture_option(mesh_texture) if extract_geometry else None
@@ -1463,7 +1501,8 @@ class ImplicitSurface(nn.Module):
                                          sparse_mesh=sparse_mesh, attributes=mesh_attributes, views=scene.views,
                                          simplify=0 if mesh_simplify is None else mesh_simplify, texture=0 if mesh_texture is None else mesh_texture,
                                          simplify_error=False if mesh_simplify_error is None else mesh_simplify_error, topology=mesh_topology,
-                                         repair=False if mesh_repair is None else mesh_repair, smooth=False if mesh_smooth is None else mesh_smooth)
+                                         repair=False if mesh_repair is None else mesh_repair, smooth=False if mesh_smooth is None else mesh_smooth,
+                                         self_intersections=mesh_self_intersections)
             outputs["vertices"], outputs["triangles"] = mesh[0], mesh[1]
             for name, values in ((mesh[2] or {}) if len(mesh) >= 3 else {}).items():
                 outputs["vertex_" + name] = values

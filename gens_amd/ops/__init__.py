@@ -35,6 +35,7 @@ is what it was when ops was one module:
     ops.mesh_repair  K38: mesh repair: duplicate faces, pinches and non-manifold edges split, small components, orientation, small holes (repair_mesh).
     ops.mesh_fairing  K39: mesh fairing: Laplacian / Taubin smoothing with uniform or cotangent weights (smooth_mesh), mesh_laplacian, mesh_roughness.
     ops.winding   K40: generalised winding numbers, exact or with a bounded far field (build_winding_plan, winding_number), and the inside test (mesh_inside).
+    ops.mesh_intersect  K41: self-intersections: which pairs of faces intersect, decided exactly or reported undecided (mesh_self_intersections).
 """
 from .base import *  # noqa: F401,F403
 from .volume import *  # noqa: F401,F403
@@ -62,3 +63,4 @@ from .mesh_distance import *  # noqa: F401,F403
 from .mesh_topology import *  # noqa: F401,F403
 from .mesh_repair import *  # noqa: F401,F403
 from .mesh_fairing import *  # noqa: F401,F403
+from .mesh_intersect import *  # noqa: F401,F403

@@ -73,7 +73,7 @@ const char* gens_last_error(void);
  *       gens_mesh_edge_classify, gens_mesh_fan_pairs, gens_mesh_vertex_classify, gens_mesh_pseudonormals, gens_mesh_distance_sign, and K38's
  *       gens_mesh_face_keys, gens_mesh_split_corners, gens_mesh_orient_pairs, gens_mesh_apply_flips, gens_mesh_loop_centroids,
  *       gens_mesh_fill_emit, and K39's gens_mesh_corner_cot, gens_mesh_edge_weights, gens_mesh_laplacian_step, gens_mesh_dihedral, and K40's
- *       gens_mesh_winding_moments, gens_mesh_winding_number. */
+ *       gens_mesh_winding_moments, gens_mesh_winding_number, and K41's gens_mesh_isect_faces, gens_mesh_isect_count, gens_mesh_isect_emit. */
 int gens_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -1615,6 +1615,84 @@ typedef struct {
 int gens_mesh_winding_moments(const gens_winding_plan* plan, void* stream);
 int gens_mesh_winding_number(const gens_winding_plan* plan, const double* queries, int64_t n_queries, double beta, double* w,
                              double* bound /* (n) or NULL */, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * K41  Self-intersections of a triangle mesh: which pairs of its faces intersect, decided exactly or not at all
+ *      (ops.mesh_self_intersections, io.mesh_report(self_intersections=True), python -m gens_amd.mesh_report --self-intersections,
+ *      ImplicitSurface.extract_geometry(self_intersections=True)), csrc/k41_mesh_intersect.hip.  tests/mesh_intersect_reference.py decides
+ *      the same question in rational arithmetic from the set definition.  A report only: nothing is removed or repaired.
+ *      vertices (V, 3) float64, triangles (T, 3) int32; V < 2^31 and 3 T < 2^31.  VALID: K37's rule (three different indices, all in [0, V)).
+ *
+ *   Definitions, in exact real arithmetic on the float64 coordinates.  A face is the closed convex hull of its three corner positions.
+ *     1. A valid face (a, b, c) is DEGENERATE when (b - a) x (c - a) is exactly the zero vector.  Degenerate faces are counted and take
+ *        part in no pair (marching cubes emits them).
+ *     2. The AABB of a face is the component-wise min / max of its corners (exact in float64).  A CANDIDATE is a pair s < t of valid faces
+ *        that are not degenerate, share k < 3 vertex INDICES, and whose closed AABBs overlap (<= on all three axes).  A pair with k = 3 is a
+ *        duplicate in K38's sense: counted (duplicate_pairs), not a candidate.  Sharing is by index only: two unwelded vertices at one
+ *        position are not shared, and faces touching there intersect.
+ *     3. A candidate pair INTERSECTS iff: k = 0: Ts and Tt have a common point; k = 1 (vertex v): they have a common point other than v's
+ *        position; k = 2 (edge e): they have a common point that is not on the segment e (a flat fold).
+ *     4. PREDICATE FORM, what the kernel evaluates (derived in DESIGN.md, section 5r).  orient3d(a, b, c, d) = det [a - d; b - d; c - d]
+ *        = (a_z - d_z) ((b_x - d_x)(c_y - d_y) - (c_x - d_x)(b_y - d_y)) + (b_z - d_z) ((c_x - d_x)(a_y - d_y) - (a_x - d_x)(c_y - d_y))
+ *        + (c_z - d_z) ((a_x - d_x)(b_y - d_y) - (b_x - d_x)(a_y - d_y)); orient2d(p, q, r) = (p_u - r_u)(q_v - r_v) - (p_v - r_v)(q_u - r_u).
+ *        k = 0: some edge of one face meets the other closed face (6 segment-face tests: the 6 plane sides orient3d(face, corner) and the
+ *               9 edge-edge values orient3d(s_i, s_i+1, t_j, t_j+1), each used by both directions -- all 15 four-subsets of the six corners).
+ *        k = 1: with Ts = (v, a, b), Tt = (v, c, d): segment ab meets Tt or segment cd meets Ts.
+ *        k = 2: with e = ab and the opposite corners c, d: orient3d(a, b, c, d) = 0 and ((b - a) x (c - a)) . ((b - a) x (d - a)) > 0.
+ *        A closed segment pq meets a face (a, b, c) that is not degenerate: the plane signs of p and q (orient3d(a, b, c, .)) strictly
+ *        equal: no.  Opposite, or exactly one zero: yes iff orient3d(p, q, a, b), orient3d(p, q, b, c), orient3d(p, q, c, a) are all >= 0
+ *        or all <= 0.  Both zero: in two dimensions, after dropping the first axis whose component of (b - a) x (c - a) is certainly not
+ *        zero: an end of pq in the closed face (three orient2d against the face's own orientation), or pq meets an edge (two closed
+ *        segments meet iff neither has both ends strictly on one side of the other; four zeros: on one line, they meet iff their boxes
+ *        do -- exact coordinate comparisons).
+ *     5. CERTIFIED SIGNS.  Every predicate returns -, 0, + or ?.  It is evaluated in float64, every operation rounded once (the file is
+ *        built without contraction), as a tree of height h: h = 3 for orient2d (difference, product, difference), h = 6 for orient3d and
+ *        the k = 2 dot product (difference, product, difference, product, sum, sum).  By induction over the tree |computed - exact| <=
+ *        ((1 + e)^h - 1) P, e = 2^-53, P = the tree with every operation replaced by the sum of absolute values (the permanent), and the
+ *        permanent as computed is >= (1 - e)^h P, so |computed - exact| <= c e P~ with c = h + 1: c = 4 for orient2d, 7 for the two others,
+ *        taken as 8.  |value| > c 2^-53 P~ (and |value| > 2^-600, P~ finite: no underflow or overflow can have voided the bound, given (6))
+ *        gives the sign.  Otherwise the predicate is evaluated again with error-free transformations -- two_sum for each difference and sum,
+ *        fma for each product's tail, a product that is not 0 and below 2^-900 counting as inexact --: if every operation was exact the
+ *        value is the exact one and its sign (0 included) is returned; else ?.  There is no expansion-arithmetic fallback.
+ *        A pair whose decision needs a ? is UNDECIDED; the decision does not wait for predicates it does not need: one face strictly on
+ *        one side of the other's plane (for k = 1: its two other corners) decides DISJOINT alone; for k = 2 a dot product that is
+ *        certainly <= 0 decides DISJOINT whatever orient3d says, and a certainly non-zero orient3d whatever the dot product says; a
+ *        segment whose ends are strictly on one side meets nothing; three edge signs of which two certainly differ say no as soon as one
+ *        end of the segment is certainly off the plane.
+ *     6. A valid face whose degeneracy cannot be certified -- some component of (b - a) x (c - a) is ?, and none is certainly non-zero --
+ *        is UNCERTAIN; so is a valid face with a coordinate that is not finite or beyond 2^100 in magnitude.  It is counted, it is
+ *        treated as not degenerate in (2), and all its candidate pairs are UNDECIDED.
+ *     7. The first face of a pair in (4) is the one whose index row (i0, i1, i2) is lexicographically smaller, not the one with the
+ *        smaller face number: a pair's verdict does not depend on how the faces are numbered.
+ *   Broad phase over K23's gens_mesh_grid as ops.build_mesh_grid builds it: a candidate is processed in exactly one cell, the one that
+ *     holds the lower corner of the intersection of the two AABBs: per axis max(i0_s, i0_t) with i0 = gens_mesh_grid_count's
+ *     clamp(floor((min - lo) / cell - 1e-5)) evaluated by the same float64 expression on the same float32 box.  That expression is
+ *     monotone in the coordinate, and the upper index i1 uses + 1e-5: min_s <= max_t gives i0_s <= i1_t, so the cell lies in both faces'
+ *     ranges, i.e. in both lists, and no other cell claims the pair: exactly once, without atomics.
+ *
+ *   gens_mesh_isect_faces: one thread per face -> face_class (T) uint8: 0 not valid, 1 ordinary, 2 degenerate, 3 uncertain; face_box
+ *     (T, 6) float64: min x, y, z, max x, y, z (zeros for a face that is not valid).
+ *   gens_mesh_isect_count: one lane per entry of the cell lists (n_entries = cell_start[cells]); the lane of (cell, position x) walks the
+ *     positions y > x of its cell, 128 per workgroup row (gridDim.y = ceil(longest_list / 128), at most 65535; rows stride over the
+ *     rest), so a long list is spread over its entries' lanes and over workgroups.  ACCUMULATES into: cell_counts (cells, 2) int32: the
+ *     pairs the cell will emit, intersecting and undecided; totals (3) int64: candidates, duplicate pairs, candidates decided DISJOINT
+ *     by one strict plane separation alone; face_flags (4 ceil(T / 4)) uint8, 4-byte aligned (integer atomicOr on its words): bit 0 for a
+ *     face of an intersecting pair, bit 1 of an undecided one.  face_class and face_box: gens_mesh_isect_faces' of the same mesh.
+ *   gens_mesh_isect_emit: the same walk; pairs (n_out, 2) int32 (s < t) and kinds (n_out) uint8 (1 intersecting, 2 undecided) at
+ *     out_start[cell] + a ticket from cursor[cell]; out_start (cells + 1) int32 = the exclusive scan of cell_counts' row sums, cursor
+ *     (cells) int32 zero-filled, n_out = out_start[cells].  The order inside a cell is not defined: the op sorts by (s << 32) | t.
+ *   Arguments are checked before any launch.  GENS_EINVAL: a null pointer that a launch would read or write, a negative size, face_flags
+ *     or totals misaligned.  GENS_ELIMIT: V, 3 T, n_entries or n_out >= 2^31; a grid outside K23's limits.  T = 0, n_entries = 0 (and
+ *     n_out = 0 for emit) succeed without a launch.  Indices in cell_faces and triangles outside their ranges are skipped, never read
+ *     through.  The ABI version stays 12: no existing entry changes.
+ * ---------------------------------------------------------------------------------------------------------- */
+int gens_mesh_isect_faces(const double* vertices, int64_t n_vertices, const int32_t* triangles, int64_t n_faces, uint8_t* face_class,
+                          double* face_box, void* stream);
+int gens_mesh_isect_count(const gens_mesh_grid* grid, int64_t n_vertices, int64_t n_entries, int64_t longest_list, const uint8_t* face_class,
+                          const double* face_box, int32_t* cell_counts, int64_t* totals, uint8_t* face_flags, void* stream);
+int gens_mesh_isect_emit(const gens_mesh_grid* grid, int64_t n_vertices, int64_t n_entries, int64_t longest_list, const uint8_t* face_class,
+                         const double* face_box, const int32_t* out_start, int32_t* cursor, int64_t n_out, int32_t* pairs, uint8_t* kinds,
+                         void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * K14  C (m x n) = A^T B for tall row-major operands A (k x m), B (k x n), k >> m, n: the weight-gradient product of the training
